@@ -16,9 +16,14 @@ Workload (one "step" = one pass of the hot path over one batch):
   the job's algorithmic bytes / wall time per step.  (--scaling weak gives
   every rank its own model-sized job instead.)
 
-Reported next to it (rank 0, N=1): the roofline of the kernel (HIP events on
-the launch stream), and the reference's CPU op sequence (oracle port) timed on
-this host on the same inputs, whose result is also checked bit for bit.
+A plain run sets up, warms up, times the steps and prints the result line, with
+the roofline of the kernel from the HIP events of the timed steps.  ``--full``
+adds the legs beside the headline (rank 0, N=1): the committed profile's
+traffic, the host-inclusive and variant-server legs, and the reference's CPU op
+sequence (oracle port) timed on this host on the same inputs, whose result is
+also checked bit for bit; at N>1 the parity check against the one-GPU kernel
+and the server's in-process multi-GPU leg.  ``--dump-outputs DIR`` writes the
+last timed step's results as ``.npy`` files.
 """
 
 from __future__ import annotations
@@ -50,6 +55,14 @@ def parse():
     p.add_argument("--variant", type=int, default=None, help="kernel variant (tuning)")
     p.add_argument("--sweep", action="store_true", help="time every kernel variant, interleaved")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: the committed "
+                        "profile's roofline fields, the host-inclusive, variant-reduction and CPU-baseline legs "
+                        "(N = 1), the parity check and the engine-devices leg (N > 1); the --no-* options trim it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed (the new model's fp32 arena and "
+                        "its int64 entries' results) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed "
+                        "seeded sample of a larger array); the same arguments give the same inputs in every run")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-host-inclusive", action="store_true")
     p.add_argument("--cpu-reps", type=int, default=3)
@@ -705,7 +718,13 @@ def main():
 
     value_gbs = job_bytes * args.steps / wall / 1e9
     variant = args.variant if args.variant is not None else 0
-    summ = pmc_traffic(alg_bytes, kernel_signature(variant)) if args.codec == "native" else None
+    if args.dump_outputs:
+        # what a caller of the timed path holds after the last step: the new model (N > 1: as gathered)
+        got_f, got_i = (out_f[: layout.n_f32], out_i[: layout.n_i64]) if plan is None else xchg.assemble(gathered)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"model_f32": got_f, "model_i64_entries": got_i})
+        del got_f, got_i
+    summ = pmc_traffic(alg_bytes, kernel_signature(variant)) if args.full and args.codec == "native" else None
     achieved = alg_bytes / (kernel_ms_max * 1e-3) / 1e9
     prof = profile_roofline(summ, alg_bytes, kernel_ms_max, wall / args.steps * 1e3)
 
@@ -756,8 +775,8 @@ def main():
         },
     }
 
-    if args.codec != "native":
-        args.no_host_inclusive = args.no_cpu_baseline = True
+    if args.codec != "native" or not args.full:
+        args.no_host_inclusive = args.no_cpu_baseline = args.no_variants = args.no_engine_devices_leg = True
     run_variants = rank == 0 and world == 1 and not args.no_variants and args.config == "C2" and args.codec == "native"
     if run_variants and args.variants_first:
         progress("variant reductions leg")
@@ -781,7 +800,7 @@ def main():
         result["parity"] = result["cpu_baseline"].pop("parity")
 
     exit_code = 0
-    if plan is not None:
+    if plan is not None and args.full:
         # outside the timed region: the model every rank gathered in the last step, in model order,
         # must be the one-GPU fused kernel's result on the same global job (rank 0 recomputes it), bit
         # for bit, and every rank must hold the same bits
@@ -818,6 +837,29 @@ def main():
         print(json.dumps(result), flush=True)
     if exit_code:
         sys.exit(exit_code)
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Write each result array as ``path/<name>.npy`` (float32), at most DUMP_LIMIT_BYTES in all.
+
+    Arrays that fit are written whole.  Otherwise each is cut to its share of the limit: a sorted
+    sample of positions drawn by a generator seeded with the array's length alone, so two runs (or
+    two builds) with the same arguments write the same positions.
+    """
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # the .npy headers count too
+    for name, t in arrays.items():
+        t = t.reshape(-1).to(torch.float32)
+        if total > budget:
+            keep = max(1, int(budget / total * t.numel()) - 1)
+            if keep < t.numel():
+                idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), size=keep))
+                t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
 
 
 def bits_digest(f: torch.Tensor, i: torch.Tensor) -> list[int]:

@@ -233,7 +233,7 @@ def test_bench_launch_timeout_kills_the_tree_and_reports_phases():
 def test_bench_self_launch_two_ranks_on_gpu():
     """The N > 1 bench from a plain ``python bench.py --gpus 2`` on the one-GPU box (gloo rehearsal: the ranks share
     the GPU): one parsed line with n_gpus == 2 and the per-rank algorithmic bytes counted."""
-    lines, err = _bench_lines(["--gpus", "2", "--steps", "3", "--warmup", "1"], {}, 600)
+    lines, err = _bench_lines(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {}, 600)
     assert len(lines) == 1, (lines, err[-2000:])
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["value"] > 0
