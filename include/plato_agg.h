@@ -76,7 +76,7 @@
 extern "C" {
 #endif
 
-#define PLATO_AGG_ABI_VERSION 4
+#define PLATO_AGG_ABI_VERSION 5
 
 #define PLATO_AGG_OK 0
 #define PLATO_AGG_EINVAL (-1)   /* bad argument (null, misaligned, K <= 0) */
@@ -534,6 +534,34 @@ int plato_agg_decode_rows(int codec, const void* const* d_src_f32, const void* c
                           const float* d_max_v, float divisor, const plato_agg_chunk* d_chunks_f32,
                           uint32_t n_chunks_f32, const plato_agg_chunk* d_chunks_i64, uint32_t n_chunks_i64,
                           size_t i64_dst_offset, float* const* d_dst, hipStream_t stream);
+
+/*
+ * Coordinate-wise robust aggregation over K client arenas: the order statistics
+ * of the reference's Byzantine-robust aggregators (examples/detector/
+ * aggregations.py, reached through detector_server.Server.aggregate_weights and
+ * server.secure_aggregation_type), which are not weighted sums.
+ *   PLATO_AGG_ROBUST_MEDIAN   aggregations.median: torch.median(X, dim=0)[0] of
+ *                             the flattened [K, d] matrix.
+ * Per coordinate j the column is c_k = x_k[j]; for the int64 region it is
+ * (float)x_k[j], round to nearest even (flatten_weights' torch.cat promotes the
+ * counters to fp32), and the result is fp32 there too.
+ *   median: NaN if any c_k is NaN, else the element at index (K-1)/2 of the
+ *   ascending order (torch's lower median).  +-inf and subnormals are ordinary
+ *   values (no flush to zero).  -0 and +0 compare equal in the reference, where
+ *   the one returned is an implementation accident; here the order is total,
+ *   -0 < +0 (the one documented divergence).  A selection: no rounding.
+ *   d_x_f32  device array of K pointers, each to n_f32 fp32 values
+ *   d_x_i64  device array of K pointers to n_i64 int64 values, or NULL when
+ *            n_i64 == 0
+ *   trim     reserved for trimmed modes (0 <= 2*trim < K); the median ignores it
+ *   d_out_f32 (16-byte aligned), d_out_i64_as_f32: the results
+ * 1 <= K <= PLATO_AGG_ROBUST_MAX_K.
+ */
+#define PLATO_AGG_ROBUST_MEDIAN 0
+#define PLATO_AGG_ROBUST_MAX_K 256
+int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                             int trim, float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32, size_t n_i64,
+                             hipStream_t stream);
 
 /*
  * Single-process RCCL communicator over the GPUs one Plato server drives.

@@ -14,7 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libplato_agg.so")
 TUNE_LIB_PATH = os.path.join(_HERE, "libplato_agg_tune.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 PLATO_AGG_OK = 0
 PLATO_AGG_EINVAL = -1
@@ -28,6 +28,8 @@ PLATO_AGG_PORT_CAST_FIRST = 1
 PLATO_AGG_SEG_NEG_DIV = 1
 PLATO_AGG_FEDADP_TABLES_READY = 1
 PLATO_AGG_DECODE = {"native": 0, "bf16": 1, "qsgd": 2}
+PLATO_AGG_ROBUST = {"median": 0}
+PLATO_AGG_ROBUST_MAX_K = 256
 
 _c_void_p = ctypes.c_void_p
 _c_size_t = ctypes.c_size_t
@@ -161,6 +163,8 @@ SIGNATURES = {
         _c_int,
         [_c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_float, _c_void_p, ctypes.c_uint32, _c_void_p,
          ctypes.c_uint32, _c_size_t, _c_void_p, _c_void_p]),
+    "plato_agg_robust_columns": (
+        _c_int, [_c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
     "plato_agg_comm_create": (_c_int, [_c_int, _c_void_p, ctypes.POINTER(_c_void_p)]),
     "plato_agg_comm_destroy": (_c_int, [_c_void_p]),
     "plato_agg_comm_size": (_c_int, [_c_void_p]),

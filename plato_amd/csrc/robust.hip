@@ -1,0 +1,129 @@
+// robust.hip — gfx950 kernel for the coordinate-wise median over K client arenas (the "Median"
+// aggregator of the reference's examples/detector/aggregations.py), exported through the C ABI in
+// include/plato_agg.h as plato_agg_robust_columns.
+//
+// Design ("Robust aggregation"):
+//  * Element-independent like FedAvg: one coordinate per lane, K coalesced dword loads through the
+//    wave-uniform pointer table (s_load).
+//  * The median is a pure selection, so there is no rounding: the result is bit-exact.  Floats are
+//    mapped to order-preserving unsigned keys (sign-flip transform: -0 < +0, -inf / +inf / subnormals
+//    are ordinary values); NaNs are tracked beside the selection (the largest |x| bit pattern of the
+//    column).
+//  * The column lives in LDS as keys[k][lane] (one-wave workgroups, K * 256 bytes, conflict-free:
+//    lane l always reads bank l), and its element of rank (K-1)/2 is found by a most-significant-bit
+//    first radix select: 32 passes, each counting the keys that agree with the bits fixed so far and
+//    have a 0 in the current bit.  Every loop is a run-time loop over K, so one kernel serves every
+//    K in 1..256 with a few dozen VGPRs and no scratch.  A lane reads only what it wrote itself: no
+//    barrier is needed.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "common.h"
+#include "plato_agg.h"
+
+namespace {
+
+int fail(int code, const std::string& msg) { return plato_agg_internal::set_error(code, msg); }
+
+typedef __attribute__((address_space(1))) const float gfloat;
+typedef __attribute__((address_space(1))) const int64_t gi64;
+
+template <class T>
+__device__ __forceinline__ T sld(const T* p, int i) {
+  return ((__attribute__((address_space(4))) const T*)p)[i];
+}
+
+// Order-preserving key of an fp32 bit pattern: unsigned ascending = the total order -nan < -inf < ...
+// < -0 < +0 < ... < +inf < +nan.
+__device__ __forceinline__ uint32_t to_key(uint32_t u) { return u ^ (uint32_t((int32_t)u >> 31) | 0x80000000u); }
+__device__ __forceinline__ uint32_t from_key(uint32_t k) { return k ^ (uint32_t((int32_t)~k >> 31) | 0x80000000u); }
+
+template <bool I64>
+struct Column;
+template <>
+struct Column<false> {
+  typedef float elem;
+  static __device__ __forceinline__ uint32_t bits(const float* p, uint64_t e) {
+    return __float_as_uint(__builtin_nontemporal_load((gfloat*)p + e));
+  }
+};
+template <>
+struct Column<true> {
+  typedef int64_t elem;
+  // torch.cat of fp32 and int64 promotes the counters to fp32, round to nearest even
+  static __device__ __forceinline__ uint32_t bits(const int64_t* p, uint64_t e) {
+    return __float_as_uint((float)__builtin_nontemporal_load((gi64*)p + e));
+  }
+};
+
+constexpr int kWave = 64;  // one-wave workgroups: lane l owns coordinate blockIdx.x * 64 + l
+
+// Lower median of column e over the K rows of `x`.
+template <bool I64>
+__global__ __launch_bounds__(kWave) void median_kernel(const typename Column<I64>::elem* const* x, int K,
+                                                        float* __restrict__ out, uint64_t n) {
+  extern __shared__ uint32_t keys[];  // [K][kWave]
+  const uint32_t lane = threadIdx.x;
+  const uint64_t e = uint64_t(blockIdx.x) * kWave + lane;
+  if (e >= n) return;
+  uint32_t mag = 0;  // max |x| bit pattern of the column: above +inf's <=> a NaN
+#pragma unroll 8
+  for (int k = 0; k < K; ++k) {
+    const uint32_t u = Column<I64>::bits(sld(x, k), e);
+    const uint32_t m = u & 0x7fffffffu;
+    mag = mag > m ? mag : m;
+    keys[k * kWave + lane] = to_key(u);
+  }
+  uint32_t rank = uint32_t(K - 1) / 2, sel = 0;
+  for (int bit = 31; bit >= 0; --bit) {
+    uint32_t below = 0;  // candidates (keys equal to sel above `bit`) with a 0 in `bit`
+#pragma unroll 8
+    for (int k = 0; k < K; ++k) below += ((keys[k * kWave + lane] ^ sel) >> bit) == 0 ? 1u : 0u;
+    if (rank >= below) {
+      rank -= below;
+      sel |= 1u << bit;
+    }
+  }
+  out[e] = __uint_as_float(mag > 0x7f800000u ? 0x7fc00000u : from_key(sel));
+}
+
+template <bool I64>
+void launch_median(const void* x, int K, float* out, size_t n, hipStream_t st) {
+  hipLaunchKernelGGL((median_kernel<I64>), dim3(uint32_t((n + kWave - 1) / kWave)), dim3(kWave),
+                     size_t(K) * kWave * sizeof(uint32_t), st, (const typename Column<I64>::elem* const*)x, K, out,
+                     uint64_t(n));
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_t* const* d_x_i64, int K, int trim,
+                             float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32, size_t n_i64,
+                             hipStream_t stream) {
+  if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "K must be in 1..256");
+  if (mode != PLATO_AGG_ROBUST_MEDIAN) return fail(PLATO_AGG_EINVAL, "unknown robust aggregation mode");
+  if (trim < 0 || 2 * trim >= K) return fail(PLATO_AGG_EINVAL, "trim must satisfy 0 <= 2*trim < K");
+  if (n_f32 && (!d_x_f32 || !d_out_f32)) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
+  if (n_i64 && (!d_x_i64 || !d_out_i64_as_f32)) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
+  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
+    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
+  if ((n_f32 && !aligned(d_out_f32, 16)) || (n_i64 && !aligned(d_out_i64_as_f32, 4)))
+    return fail(PLATO_AGG_EINVAL, "fp32 output must be 16-byte aligned (int64-as-fp32 output: 4)");
+  // one coordinate per lane, at least 64 lanes per workgroup, at most 2^31 - 1 workgroups
+  if (n_f32 / 64 >= 0x7fffffffull || n_i64 / 64 >= 0x7fffffffull)
+    return fail(PLATO_AGG_EINVAL, "more than 2^37 coordinates in one call");
+  if (n_f32) launch_median<false>(d_x_f32, K, d_out_f32, n_f32, stream);
+  if (n_i64) launch_median<true>(d_x_i64, K, d_out_i64_as_f32, n_i64, stream);
+  if (n_f32 || n_i64) {
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(PLATO_AGG_EHIP, std::string("robust_columns: ") + hipGetErrorString(err));
+  }
+  return plato_agg_internal::clear_error();
+}
+
+}  // extern "C"

@@ -475,6 +475,29 @@ class FedAvgEngine:
         rnd.launch(weights, scales)
         return rnd.result()
 
+    def aggregate_robust(self, payloads: Sequence[Mapping[str, torch.Tensor]], mode: str = "median",
+                         trim: int = 0) -> "OrderedDict[str, torch.Tensor]":
+        """The detector example's order-statistic aggregators over K native payloads, on the GPU.
+
+        ``mode="median"``: the coordinate-wise lower median (``aggregations.median``).  Returns CPU
+        float32 tensors for every entry, the int64 counters included, as the reference does.
+        """
+        k = len(payloads)
+        if k == 0:
+            raise ValueError("no client payloads to aggregate")
+        if k > _lib.PLATO_AGG_ROBUST_MAX_K:
+            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, got {k}")
+        codec = payload_codec(payloads[0])
+        if codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
+        rnd = self.begin(payloads[0], k)
+        rnd.deltas = False  # no baseline: the rows stay weights
+        for i, sd in enumerate(payloads):
+            if not rnd.adopt(i, sd):
+                rnd.put_client(i, sd)
+        rnd.launch_robust(mode, trim)
+        return rnd.result()
+
     def aggregate_deltas(self, deltas_received: Sequence[Mapping[str, torch.Tensor]],
                          weights: Sequence[float], scales: Sequence[float] | None = None
                          ) -> "OrderedDict[str, torch.Tensor]":
@@ -879,6 +902,43 @@ class AggregationRound:
         e1.record(stream)
         self._kernel_events = (e0, e1)
         self._fetch(stream, out_f, out_i, (tf, ti, w64, wi))
+
+    def launch_robust(self, mode: str = "median", trim: int = 0, order: Sequence[int] | None = None) -> None:
+        """Coordinate-wise robust aggregation of the staged client rows (``plato_agg_robust_columns``).
+
+        ``mode="median"`` is ``aggregations.median`` of the reference's detector example
+        (examples/detector/aggregations.py): ``torch.median(dim=0)`` of the flattened models, the
+        lower median per coordinate.  No baseline is read.  Every entry of the result is float32,
+        the int64 counters included (``flatten_weights`` promotes them).
+        """
+        if mode not in _lib.PLATO_AGG_ROBUST:
+            raise ValueError(f"unknown robust aggregation mode {mode!r} (supported: {sorted(_lib.PLATO_AGG_ROBUST)})")
+        if self.codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads; this round holds {self.codec} codes")
+        self._raw_only("launch_robust")
+        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else list(order)
+        slots = self._check_slots(order)
+        eng, lay = self.engine, self.layout
+        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
+        self._k = len(slots)
+        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
+        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
+        tf, ti = eng._pointer_tables(pf, pi)
+        stream = torch.cuda.current_stream(eng.device)
+        self.stager.fence(stream)
+        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
+        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        n_i = lay.n_i64
+        with self._timed("robust_" + mode, stream):
+            _lib.call("plato_agg_robust_columns", _lib.PLATO_AGG_ROBUST[mode], _ptr(tf), _ptr(ti) if n_i else None,
+                      len(slots), int(trim), _ptr(out_f), _ptr(out_i) if n_i else None, lay.n_f32, n_i,
+                      _stream_handle(stream))
+        e1.record(stream)
+        self._kernel_events = (e0, e1)
+        self._robust = True
+        self._fetch(stream, out_f, out_i, (tf, ti))
 
     def _fetch(self, stream, out_f: torch.Tensor, out_i: torch.Tensor, keep=()) -> None:
         """D2H into pooled pinned buffers, stream-ordered; result() only waits."""
@@ -1467,6 +1527,9 @@ class AggregationRound:
 
     def algorithmic_bytes(self) -> int:
         """HBM bytes of the launch: K client arenas + baseline read, result written."""
+        if getattr(self, "_robust", False):  # no baseline; the counters come back as fp32
+            lay = self.layout
+            return (self._k + 1) * lay.n_f32_data * 4 + self._k * lay.n_i64 * 8 + lay.n_i64 * 4
         return self.layout.algorithmic_bytes(self._k)
 
     def result(self) -> "OrderedDict[str, torch.Tensor]":
@@ -1478,6 +1541,7 @@ class AggregationRound:
             self.timings["kernel_ms"] = e0.elapsed_time(e1)
             self.timings["d2h_ms"] = e1.elapsed_time(self.event)
         self.timings["total_ms"] = (time.perf_counter() - self._t0) * 1e3
+        self._resolve_timers()  # launches timed with _timed and fetched by this call (launch_robust)
         host_f, host_i = self._out[0], self._out[1]
         self._out = None
         return self.layout.unpack(host_f, host_i)

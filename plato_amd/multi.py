@@ -439,9 +439,15 @@ class MultiDeviceEngine:
         rnd.launch(weights, scales, deltas=True)
         return rnd.result()
 
+    def aggregate_robust(self, payloads, mode: str = "median", trim: int = 0):
+        raise NotImplementedError("robust aggregation (median) runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""
+
+    def launch_robust(self, mode: str = "median", trim: int = 0, order=None):
+        raise NotImplementedError("robust aggregation (median) runs on one GPU: use FedAvgEngine")
 
     def __init__(self, engine: MultiDeviceEngine, layout: ArenaLayout, capacity: int, codec: str):
         self.engine = engine

@@ -1,0 +1,70 @@
+"""Byzantine-robust aggregation hook: the order-statistic aggregators of the reference's detector example.
+
+``examples/detector/detector_server.py`` dispatches ``aggregate_weights`` on
+``server.secure_aggregation_type`` to ``examples/detector/aggregations.py``.  Its ``Median`` is a
+coordinate-wise order statistic over the received models, not a weighted sum; here it runs on the GPU
+(``plato_agg_robust_columns``).  The detector server's ``weights_received`` pipeline (attack
+simulation, filters) is the base class's and runs before this hook, unchanged::
+
+    Server = make_server(base=detector_server.Server, mixin=RobustAggregationMixin)
+"""
+
+from __future__ import annotations
+
+from .. import tracing
+from ..arena import payload_codec
+from .fedavg import FusedAggregationMixin
+
+#: ``server.secure_aggregation_type`` -> ``AggregationRound.launch_robust`` mode
+ROBUST_MODES = {"Median": "median"}
+
+
+def _secure_aggregation_type():
+    try:
+        from plato.config import Config
+
+        server = Config().server
+        return getattr(server, "secure_aggregation_type", None) if hasattr(server, "secure_aggregation_type") else None
+    except Exception:  # Plato not importable / not configured: the FedAvg branch
+        return None
+
+
+class RobustAggregationMixin(FusedAggregationMixin):
+    """``aggregate_weights`` hook of the detector server: "Median" on the GPU, else the fused FedAvg."""
+
+    #: None = ``Config().server.secure_aggregation_type`` (absent: FedAvg, as in the reference)
+    secure_aggregation_type = None
+
+    def robust_aggregation_type(self):
+        own = self.secure_aggregation_type
+        return own if own is not None else _secure_aggregation_type()
+
+    async def aggregate_weights(self, updates, baseline_weights, weights_received):
+        name = self.robust_aggregation_type()
+        if name is None:  # the reference's "Fedavg is applied" branch
+            return await super().aggregate_weights(updates, baseline_weights, weights_received)
+        if name not in ROBUST_MODES:
+            raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
+                             f"(supported: {', '.join(sorted(ROBUST_MODES))})")
+        codec = payload_codec(weights_received[0])
+        if codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
+        engine = self.aggregation_engine()
+        if getattr(engine, "primary", None) is not None:
+            raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
+        try:
+            rnd = engine.begin(weights_received[0], len(weights_received))
+
+            def stage():
+                with tracing.range("plato_amd.stage"):
+                    for slot, payload in enumerate(weights_received):
+                        if not rnd.adopt(slot, payload):
+                            rnd.put_client(slot, payload)
+
+            await self._off_loop(stage)
+            with tracing.range("plato_amd.launch"):
+                rnd.launch_robust(ROBUST_MODES[name])
+            with tracing.range("plato_amd.fetch"):
+                return await self._finish(rnd)
+        finally:
+            engine.release_arrivals()

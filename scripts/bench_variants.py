@@ -9,6 +9,9 @@ launch stream), algorithmic bytes, GB/s and fraction of the 8 TB/s peak.
 * norms       plato_agg_entry_norms_f32 (FedAtt, torch CPU order): K x 4 B + 4 B; a serial
               fma chain per (client, entry, lane) — latency-bound by the largest entry
 * fedavg      the FedAvg kernel itself, for reference
+* robust_median  plato_agg_robust_columns (coordinate-wise median): K x 4 B read + 4 B written, no
+              baseline; --host-reference also times the reference's op, torch.median(X, dim=0) on the
+              already flattened [K, d] host matrix (torch.get_num_threads() threads)
 
 Usage: python scripts/bench_variants.py [--clients 128] [--reps 10]
 """
@@ -51,6 +54,8 @@ def main():
     ap.add_argument("--sumsq-list", default=None, help="comma-separated np_sumsq variants to time")
     ap.add_argument("--deltas", action="store_true",
                     help="client arenas hold x - b (delta arenas): entry norms run with a null baseline")
+    ap.add_argument("--host-reference", action="store_true",
+                    help="robust_median: also time torch.median(X, dim=0) on the flattened [K, d] matrix on this host")
     ap.add_argument("--norm-order", default="longest", choices=["longest", "layout"],
                     help="entry order of the norms launch (longest first = the engine's)")
     args = ap.parse_args()
@@ -160,6 +165,10 @@ def main():
     def run_fedavg():
         engine.launch_fedavg(layout, tf, ti, w, None, k, base.f32, base.i64, out_f, out_i, stream)
 
+    def run_robust_median():
+        _lib.call("plato_agg_robust_columns", _lib.PLATO_AGG_ROBUST["median"], _ptr(tf), _ptr(ti), k, 0, _ptr(out_f),
+                  _ptr(out_i), n_f, n_i, h)
+
     # Polaris: numpy-order sums of squares per fp32 entry (plato_agg_np_sumsq, the product kernels)
     sq_rows, sq_first, sq_chunks = [], [], 0
     for idx, e in enumerate(layout.entries):
@@ -187,6 +196,7 @@ def main():
         "norms": (run_norms, (k + 1) * n_f * 4 + (k + 1) * n_i * 8),
         "fedavg": (run_fedavg, layout.algorithmic_bytes(k)),
         "sumsq": (run_sumsq, (k + 1) * n_f * 4),
+        "robust_median": (run_robust_median, (k + 1) * n_f * 4 + k * n_i * 8 + n_i * 4),
     }
     if args.qsgd_variants or args.qsgd_list:  # tuning: every (or the listed) plato_agg_tune_fedavg_qsgd variant
         vlist = ([int(x) for x in args.qsgd_list.split(",")] if args.qsgd_list
@@ -233,6 +243,20 @@ def main():
         print(json.dumps({"kernel": name, "clients": k, "ms_median": round(med, 4), "ms_min": round(min(times[name]), 4),
                           "algorithmic_bytes": int(nbytes), "GBps": round(gbs, 1),
                           "frac_of_8TBps": round(gbs / PEAK, 4), "samples": len(times[name])}), flush=True)
+    if args.host_reference and any(name == "robust_median" for name, _, _ in selected):
+        import time
+
+        x = slab.f32[:, :n_f].cpu()  # the reference's flatten_weights output (its own cost is not timed)
+        host = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            ref = torch.median(x, dim=0)[0]
+            host.append((time.perf_counter() - t0) * 1e3)
+        run_robust_median()
+        same = bool(torch.equal(out_f[:n_f].cpu().view(torch.int32), ref.view(torch.int32)))
+        print(json.dumps({"kernel": "host_torch_median", "clients": k, "threads": torch.get_num_threads(),
+                          "ms_min": round(min(host), 1), "ms_all": [round(t, 1) for t in host],
+                          "device_result_bit_equal": same}), flush=True)
 
 
 if __name__ == "__main__":
