@@ -100,6 +100,58 @@ def test_argument_errors_are_raised_without_gpu_work():
     assert AggregationRound.fedadp_boundary_rows((1 << 21) - 1, 0) >= AggregationRound.FEDADP_MAX_BND
 
 
+def test_f64_decode_and_dots_argument_errors_are_raised_without_gpu_work():
+    """The host-side refusals of plato_agg_weighted_sum_f64, plato_agg_decode_rows and
+    plato_agg_client_dots: every call below fails a check (or has nothing to do) before any launch."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    a = 1 << 12  # any 256-byte-aligned non-null address: nothing is dereferenced on these paths
+    lib = _lib.lib()
+    # float64 weighted sum: n = 0 is a success with nothing written, K = 0 and a misaligned output are refused
+    assert lib.plato_agg_weighted_sum_f64(a, a, 3, a, 0, None) == _lib.PLATO_AGG_OK
+    assert lib.plato_agg_weighted_sum_f64(None, None, 3, None, 0, None) == _lib.PLATO_AGG_OK
+    with pytest.raises(ValueError, match="K must be"):
+        _lib.call("plato_agg_weighted_sum_f64", a, a, 0, a, 5, None)
+    with pytest.raises(ValueError, match="null"):
+        _lib.call("plato_agg_weighted_sum_f64", a, None, 3, a, 5, None)
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        _lib.call("plato_agg_weighted_sum_f64", a, a, 3, a + 8, 5, None)
+    # decode_rows: (codec, src_f32, src_i64, K, max_v, divisor, chunks_f32, n, chunks_i64, n, i64_dst_offset, dst, stream)
+    for k in (0, 65536, -1):
+        with pytest.raises(ValueError, match=r"K must be in \[1, 65535\]"):
+            _lib.call("plato_agg_decode_rows", 0, a, a, k, None, 0.0, a, 1, a, 1, 64, a, None)
+    for codec in (-1, 3):
+        with pytest.raises(ValueError, match="bad codec"):
+            _lib.call("plato_agg_decode_rows", codec, a, a, 2, None, 0.0, a, 1, a, 1, 64, a, None)
+    with pytest.raises(ValueError, match="null"):
+        _lib.call("plato_agg_decode_rows", 0, a, a, 2, None, 0.0, a, 1, a, 1, 64, None, None)
+    with pytest.raises(ValueError, match="null"):
+        _lib.call("plato_agg_decode_rows", 1, a, a, 2, None, 0.0, None, 1, a, 1, 64, a, None)
+    with pytest.raises(ValueError, match="QSGD needs max_v"):
+        _lib.call("plato_agg_decode_rows", 2, a, a, 2, None, 63.0, a, 1, a, 1, 64, a, None)
+    with pytest.raises(ValueError, match="non-zero divisor"):
+        _lib.call("plato_agg_decode_rows", 2, a, a, 2, a, 0.0, a, 1, a, 1, 64, a, None)
+    for codec, mv, divisor in ((0, None, 0.0), (1, None, 0.0), (2, a, 63.0)):  # zero chunks: success, no launch
+        assert lib.plato_agg_decode_rows(codec, a, a, 2, mv, divisor, a, 0, a, 0, 64, a, None) == _lib.PLATO_AGG_OK
+    # client_dots: (x, x_i64, K, base, base_i64, v, v_i64, n_f32, n_i64, workspace, out, stream)
+    assert lib.plato_agg_client_dots_workspace(0, 1024) == 8 and lib.plato_agg_client_dots_workspace(3, 0) == 7 * 8
+    assert lib.plato_agg_client_dots_workspace(3, 4 * 256 + 4) == 7 * 2 * 8  # one partial per 1,024 elements
+    with pytest.raises(ValueError, match="K must be"):
+        _lib.call("plato_agg_client_dots", a, None, 0, None, None, a, None, 16, 0, a, a, None)
+    for args in ((None, None, 2, None, None, a, None, 16, 0, a, a), (a, None, 2, None, None, None, None, 16, 0, a, a),
+                 (a, None, 2, None, None, a, None, 16, 0, None, a), (a, None, 2, None, None, a, None, 16, 0, a, None)):
+        with pytest.raises(ValueError, match="null pointer"):
+            _lib.call("plato_agg_client_dots", *args, None)
+    for args in ((a, None, 2, None, None, a, a, 16, 1, a, a), (a, a, 2, None, None, a, None, 16, 1, a, a),
+                 (a, a, 2, a, None, a, a, 16, 1, a, a)):
+        with pytest.raises(ValueError, match="null int64 pointer"):
+            _lib.call("plato_agg_client_dots", *args, None)
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        _lib.call("plato_agg_client_dots", a, None, 2, None, None, a + 4, None, 16, 0, a, a, None)
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        _lib.call("plato_agg_client_dots", a, None, 2, a + 8, None, a, None, 16, 0, a, a, None)
+
+
 def test_engine_refuses_without_gpu():
     import torch
 
