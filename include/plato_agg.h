@@ -64,6 +64,11 @@
  *                                 attentive aggregation (fedatt_algorithm.py:44-69)
  *                                 and FedAdp's global-gradient pass
  *                                 (fedadp_server.py:43-50)
+ *   plato_agg_robust_columns   <- the detector example's coordinate-wise median
+ *                                 (examples/detector/aggregations.py:55-73)
+ *   plato_agg_pairwise_sqdist, <- the detector example's Multi-Krum: the distance
+ *   plato_agg_mean_rows           loop of every selection step and the mean of the
+ *                                 selected models (aggregations.py:176-230)
  */
 #ifndef PLATO_AGG_H
 #define PLATO_AGG_H
@@ -562,6 +567,64 @@ int plato_agg_decode_rows(int codec, const void* const* d_src_f32, const void* c
 int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
                              int trim, float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32, size_t n_i64,
                              hipStream_t stream);
+
+/*
+ * Multi-Krum (examples/detector/aggregations.py:176-230, "Multi-krum" of
+ * server.secure_aggregation_type): the K x K squared L2 distances over the whole
+ * flattened model, a selection on the host (plato_amd/krum.py), and the mean of
+ * the selected rows.  "Krum" and "Bulyan" are not provided.
+ *
+ * plato_agg_pairwise_sqdist  <- the distance loop of every selection step
+ *                               (aggregations.py:185-192):
+ *                                 torch.norm((remaining - weight), dim=1) ** 2
+ *                               for every remaining weight, once for all K rows.
+ *   d_out[i*K + j] = sum over e of fp32(c_i[e] - c_j[e])^2, over both regions, with
+ *   c_k[e] = x_k[e] in the fp32 region and (float)x_k[e] (round to nearest even)
+ *   in the int64 region, as flatten_weights' torch.cat promotes the counters.
+ *   Each difference is one separately rounded fp32 subtraction (the reference's
+ *   `remaining - weight`); never the Gram form |a|^2 + |b|^2 - 2ab, which cancels
+ *   what the selection needs when clients are a common model plus small noise.
+ *   The squares are accumulated per lane by __fmaf_rn chains of at most
+ *   PLATO_AGG_PAIRDIST_CHAIN terms; chain results are added in float64, in a fixed
+ *   order: across the lanes of a wave, over the chains of a workgroup's
+ *   coordinate chunk, then over the chunks (through d_workspace, by a final
+ *   kernel).  No atomics.  |d_out - exact sum of the fp32 differences' squares|
+ *   <= ((PLATO_AGG_PAIRDIST_CHAIN + 1) * 2^-24 + D * 2^-53) * d_out, D = n_f32 + n_i64
+ *   (the reference's own fp32 sum is within D * 2^-24).
+ *   Properties: (a) bitwise repeatable from run to run; (b) d_out[i][j] depends
+ *   only on rows i and j and on (n_f32, n_i64), not on K, on where the pair falls
+ *   in the tiling or on the order of the pointer table: a permuted table gives
+ *   the bitwise permuted matrix, and d_out[i][j] == d_out[j][i] bitwise; (c) the
+ *   diagonal is exactly +0, whatever row i holds; (d) off the diagonal NaN and
+ *   +-inf propagate by IEEE rules (inf - inf = NaN).
+ *   d_x_f32, d_x_i64   device arrays of K row pointers (d_x_i64 NULL when n_i64 == 0)
+ *   d_workspace        plato_agg_pairwise_sqdist_workspace(K, n_f32, n_i64) bytes
+ *                      (0: bad arguments), 256-byte aligned
+ *   d_out              K * K doubles, row-major, 16-byte aligned
+ *   1 <= K <= PLATO_AGG_ROBUST_MAX_K; fewer than 2^38 coordinates per region.
+ *
+ * plato_agg_mean_rows  <- torch.mean(candidates, dim=0) (aggregations.py:218)
+ *   for every coordinate e: acc = +0; for r = 0..m-1 in table order:
+ *   acc = acc + c_r[e] (fp32, separately rounded); out[e] = acc / (float)m (IEEE
+ *   division).  fp32 results for both regions.  1 <= m <= 256.
+ *
+ * Two documented divergences from the reference, both by rounding or by an
+ * accident of the reference only:
+ *   - the mean is the sequential row sum over m; torch.mean on the CPU is
+ *     torch.sum(X, dim=0) / fp32(m) with ATen's blocked row order, which equals
+ *     the sequential sum only for small m.  Both are within the any-order
+ *     summation bound 2(m-1) * 2^-24 * sum|x| / m of each other.
+ *   - the selection breaks score ties towards the lowest client index (the
+ *     reference's torch.argsort is not stable).
+ */
+#define PLATO_AGG_PAIRDIST_CHAIN 128
+size_t plato_agg_pairwise_sqdist_workspace(int K, size_t n_f32, size_t n_i64);
+int plato_agg_pairwise_sqdist(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                              size_t n_f32, size_t n_i64, void* d_workspace,
+                              double* d_out /* K*K, row-major */, hipStream_t stream);
+int plato_agg_mean_rows(const float* const* d_x_f32, const int64_t* const* d_x_i64, int m,
+                        float* d_out_f32, float* d_out_i64_as_f32,
+                        size_t n_f32, size_t n_i64, hipStream_t stream);
 
 /*
  * Single-process RCCL communicator over the GPUs one Plato server drives.

@@ -30,6 +30,7 @@ PLATO_AGG_FEDADP_TABLES_READY = 1
 PLATO_AGG_DECODE = {"native": 0, "bf16": 1, "qsgd": 2}
 PLATO_AGG_ROBUST = {"median": 0}
 PLATO_AGG_ROBUST_MAX_K = 256
+PLATO_AGG_PAIRDIST_CHAIN = 128
 
 _c_void_p = ctypes.c_void_p
 _c_size_t = ctypes.c_size_t
@@ -165,6 +166,11 @@ SIGNATURES = {
          ctypes.c_uint32, _c_size_t, _c_void_p, _c_void_p]),
     "plato_agg_robust_columns": (
         _c_int, [_c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
+    "plato_agg_pairwise_sqdist_workspace": (_c_size_t, [_c_int, _c_size_t, _c_size_t]),
+    "plato_agg_pairwise_sqdist": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_size_t, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
+    "plato_agg_mean_rows": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
     "plato_agg_comm_create": (_c_int, [_c_int, _c_void_p, ctypes.POINTER(_c_void_p)]),
     "plato_agg_comm_destroy": (_c_int, [_c_void_p]),
     "plato_agg_comm_size": (_c_int, [_c_void_p]),
@@ -243,7 +249,10 @@ _tune = None
 
 def _bind(handle, signatures):
     for name, (restype, argtypes) in signatures.items():
-        fn = getattr(handle, name)
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:  # a library built before the symbol was added
+            raise RuntimeError(f"plato_amd: {handle._name} lacks {name}; rebuild it") from None
         fn.restype = restype
         fn.argtypes = argtypes
 

@@ -498,6 +498,30 @@ class FedAvgEngine:
         rnd.launch_robust(mode, trim)
         return rnd.result()
 
+    def aggregate_multi_krum(self, payloads: Sequence[Mapping[str, torch.Tensor]], f: int = 2
+                             ) -> "OrderedDict[str, torch.Tensor]":
+        """The detector example's ``Multi-krum`` (``aggregations.multi_krum``) over K native payloads, on
+        the GPU: the mean of the ``K - 2f - 2`` clients its distance scores select.  Returns CPU float32
+        tensors for every entry, the int64 counters included, as the reference does."""
+        k = len(payloads)
+        if k == 0:
+            raise ValueError("no client payloads to aggregate")
+        if k > _lib.PLATO_AGG_ROBUST_MAX_K:
+            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, got {k}")
+        if k <= 2 * int(f) + 2:
+            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, got {k}")
+        codec = payload_codec(payloads[0])
+        if codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
+        rnd = self.begin(payloads[0], k)
+        rnd.deltas = False  # no baseline: the rows stay weights
+        for i, sd in enumerate(payloads):
+            if not rnd.adopt(i, sd):
+                rnd.put_client(i, sd)
+        rnd.launch_multi_krum(f)
+        self.last_selected = rnd.selected
+        return rnd.result()
+
     def aggregate_deltas(self, deltas_received: Sequence[Mapping[str, torch.Tensor]],
                          weights: Sequence[float], scales: Sequence[float] | None = None
                          ) -> "OrderedDict[str, torch.Tensor]":
@@ -939,6 +963,86 @@ class AggregationRound:
         self._kernel_events = (e0, e1)
         self._robust = True
         self._fetch(stream, out_f, out_i, (tf, ti))
+
+    def _distance_rows(self, what: str, order: Sequence[int] | None):
+        """(slots, fp32 pointer table, int64 pointer table, stream) of a distance-based launch, the
+        stream ordered behind the staged copies.  The refusals of :meth:`launch_robust`."""
+        if self.codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads; this round holds {self.codec} codes")
+        self._raw_only(what)
+        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else list(order)
+        slots = self._check_slots(order)
+        if len(slots) > _lib.PLATO_AGG_ROBUST_MAX_K:
+            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, "
+                             f"got {len(slots)}")
+        if not self.layout.packed:
+            raise ValueError(f"{what} sums over the whole fp32 region: the arena must have no alignment padding")
+        eng = self.engine
+        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
+        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
+        tf, ti = eng._pointer_tables(pf, pi)
+        stream = torch.cuda.current_stream(eng.device)
+        self.stager.fence(stream)
+        return slots, tf, ti, stream
+
+    def _pairwise_sqdist(self, k: int, tf, ti, stream) -> np.ndarray:
+        eng, lay = self.engine, self.layout
+        n_i = lay.n_i64
+        nbytes = _lib.lib().plato_agg_pairwise_sqdist_workspace(k, lay.n_f32, n_i)
+        work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=eng.device)
+        out = torch.empty((k, k), dtype=torch.float64, device=eng.device)
+        with self._timed("pairwise_sqdist", stream):
+            _lib.call("plato_agg_pairwise_sqdist", _ptr(tf), _ptr(ti) if n_i else None, k, lay.n_f32, n_i,
+                      _ptr(work), _ptr(out), _stream_handle(stream))
+        dist = out.cpu().numpy()  # stream-ordered, blocking: the selection runs on the host
+        del work
+        return dist
+
+    def launch_pairwise_sqdist(self, order: Sequence[int] | None = None) -> np.ndarray:
+        """The [K, K] float64 matrix of squared L2 distances between the staged client rows, over the
+        whole flattened model (``plato_agg_pairwise_sqdist``): entry [i, j] is
+        ``torch.norm(x_order[i] - x_order[j]) ** 2`` of the reference's distance-based aggregators and
+        detectors (examples/detector/aggregations.py:185-192), with fp32 differences and a float64
+        sum.  Synchronises: the matrix is returned on the host."""
+        slots, tf, ti, stream = self._distance_rows("launch_pairwise_sqdist", order)
+        dist = self._pairwise_sqdist(len(slots), tf, ti, stream)
+        self._resolve_timers()
+        return dist
+
+    def launch_multi_krum(self, f: int = 2, order: Sequence[int] | None = None) -> None:
+        """``aggregations.multi_krum`` of the reference's detector example over the staged client rows:
+        the distance matrix on the device, the selection on the host (``plato_amd.krum``), then the mean
+        of the selected rows in selection order (``plato_agg_mean_rows``).  ``self.selected`` holds the
+        selected client slots in selection order.  No baseline is read; every entry of the result is
+        float32, the int64 counters included."""
+        from .krum import multi_krum_select
+
+        slots, tf, ti, stream = self._distance_rows("launch_multi_krum", order)
+        if len(slots) <= 2 * int(f) + 2:
+            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, got {len(slots)}")
+        eng, lay = self.engine, self.layout
+        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
+        self._k = len(slots)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        dist = self._pairwise_sqdist(len(slots), tf, ti, stream)
+        t0 = time.perf_counter()
+        picks = multi_krum_select(dist, f)
+        self.timings["select_ms"] = (time.perf_counter() - t0) * 1e3
+        self.selected = [slots[p] for p in picks]
+        self._k = len(slots) + len(picks)  # algorithmic_bytes: K rows for the distances, then the selected ones again
+        sf, si = eng._pointer_tables(np.asarray([self._pf[i] for i in self.selected], dtype=np.int64),
+                                     np.asarray([self._pi[i] for i in self.selected], dtype=np.int64))
+        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
+        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
+        n_i = lay.n_i64
+        with self._timed("mean_rows", stream):
+            _lib.call("plato_agg_mean_rows", _ptr(sf), _ptr(si) if n_i else None, len(picks), _ptr(out_f),
+                      _ptr(out_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
+        e1.record(stream)
+        self._kernel_events = (e0, e1)
+        self._robust = True
+        self._fetch(stream, out_f, out_i, (tf, ti, sf, si))
 
     def _fetch(self, stream, out_f: torch.Tensor, out_i: torch.Tensor, keep=()) -> None:
         """D2H into pooled pinned buffers, stream-ordered; result() only waits."""

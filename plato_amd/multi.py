@@ -442,12 +442,21 @@ class MultiDeviceEngine:
     def aggregate_robust(self, payloads, mode: str = "median", trim: int = 0):
         raise NotImplementedError("robust aggregation (median) runs on one GPU: use FedAvgEngine")
 
+    def aggregate_multi_krum(self, payloads, f: int = 2):
+        raise NotImplementedError("robust aggregation (Multi-Krum) runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""
 
     def launch_robust(self, mode: str = "median", trim: int = 0, order=None):
         raise NotImplementedError("robust aggregation (median) runs on one GPU: use FedAvgEngine")
+
+    def launch_pairwise_sqdist(self, order=None):
+        raise NotImplementedError("pairwise distances run on one GPU: use FedAvgEngine")
+
+    def launch_multi_krum(self, f: int = 2, order=None):
+        raise NotImplementedError("robust aggregation (Multi-Krum) runs on one GPU: use FedAvgEngine")
 
     def __init__(self, engine: MultiDeviceEngine, layout: ArenaLayout, capacity: int, codec: str):
         self.engine = engine

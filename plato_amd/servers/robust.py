@@ -3,8 +3,11 @@
 ``examples/detector/detector_server.py`` dispatches ``aggregate_weights`` on
 ``server.secure_aggregation_type`` to ``examples/detector/aggregations.py``.  Its ``Median`` is a
 coordinate-wise order statistic over the received models, not a weighted sum; here it runs on the GPU
-(``plato_agg_robust_columns``).  The detector server's ``weights_received`` pipeline (attack
-simulation, filters) is the base class's and runs before this hook, unchanged::
+(``plato_agg_robust_columns``).  Its ``Multi-krum`` scores every client by its squared distances to the
+others and averages the selected ones: distances and mean on the GPU (``plato_agg_pairwise_sqdist``,
+``plato_agg_mean_rows``), the selection on the host (``plato_amd.krum``).  The detector server's
+``weights_received`` pipeline (attack simulation, filters) is the base class's and runs before this
+hook, unchanged::
 
     Server = make_server(base=detector_server.Server, mixin=RobustAggregationMixin)
 """
@@ -17,6 +20,9 @@ from .fedavg import FusedAggregationMixin
 
 #: ``server.secure_aggregation_type`` -> ``AggregationRound.launch_robust`` mode
 ROBUST_MODES = {"Median": "median"}
+#: ``server.secure_aggregation_type`` -> f of ``AggregationRound.launch_multi_krum``: the reference's
+#: hard-coded ``num_attackers_selected`` (aggregations.py:180)
+MULTI_KRUM = {"Multi-krum": 2}
 
 
 def _secure_aggregation_type():
@@ -30,7 +36,8 @@ def _secure_aggregation_type():
 
 
 class RobustAggregationMixin(FusedAggregationMixin):
-    """``aggregate_weights`` hook of the detector server: "Median" on the GPU, else the fused FedAvg."""
+    """``aggregate_weights`` hook of the detector server: "Median" and "Multi-krum" on the GPU, else the
+    fused FedAvg."""
 
     #: None = ``Config().server.secure_aggregation_type`` (absent: FedAvg, as in the reference)
     secure_aggregation_type = None
@@ -43,9 +50,9 @@ class RobustAggregationMixin(FusedAggregationMixin):
         name = self.robust_aggregation_type()
         if name is None:  # the reference's "Fedavg is applied" branch
             return await super().aggregate_weights(updates, baseline_weights, weights_received)
-        if name not in ROBUST_MODES:
+        if name not in ROBUST_MODES and name not in MULTI_KRUM:
             raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
-                             f"(supported: {', '.join(sorted(ROBUST_MODES))})")
+                             f"(supported: {', '.join(sorted({**ROBUST_MODES, **MULTI_KRUM}))})")
         codec = payload_codec(weights_received[0])
         if codec != "native":
             raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
@@ -63,7 +70,10 @@ class RobustAggregationMixin(FusedAggregationMixin):
 
             await self._off_loop(stage)
             with tracing.range("plato_amd.launch"):
-                rnd.launch_robust(ROBUST_MODES[name])
+                if name in MULTI_KRUM:
+                    rnd.launch_multi_krum(MULTI_KRUM[name])
+                else:
+                    rnd.launch_robust(ROBUST_MODES[name])
             with tracing.range("plato_amd.fetch"):
                 return await self._finish(rnd)
         finally:
