@@ -65,10 +65,13 @@
  *                                 and FedAdp's global-gradient pass
  *                                 (fedadp_server.py:43-50)
  *   plato_agg_robust_columns   <- the detector example's coordinate-wise median
- *                                 (examples/detector/aggregations.py:55-73)
+ *                                 (examples/detector/aggregations.py:55-73) and
+ *                                 the mean of the values nearest it that ends its
+ *                                 Trimmed-mean and Bulyan (:125-132, :238-243)
  *   plato_agg_pairwise_sqdist, <- the detector example's Multi-Krum: the distance
  *   plato_agg_mean_rows           loop of every selection step and the mean of the
- *                                 selected models (aggregations.py:176-230)
+ *                                 selected models (aggregations.py:176-230); the
+ *                                 distances serve Bulyan's selection too (:86-123)
  */
 #ifndef PLATO_AGG_H
 #define PLATO_AGG_H
@@ -555,14 +558,34 @@ int plato_agg_decode_rows(int codec, const void* const* d_src_f32, const void* c
  *   values (no flush to zero).  -0 and +0 compare equal in the reference, where
  *   the one returned is an implementation accident; here the order is total,
  *   -0 < +0 (the one documented divergence).  A selection: no rounding.
+ *   PLATO_AGG_ROBUST_NEAREST_MEAN   the last step of aggregations.trimmed_mean and
+ *                             aggregations.bulyan: the mean of the b = K - 2*trim
+ *                             values of the column nearest its lower median,
+ *                               med = torch.median(X, dim=0)[0]
+ *                               idx = torch.argsort(torch.abs(X - med), dim=0)
+ *                               torch.mean(X[idx, arange(d)][:b], dim=0)
+ *   nearest mean: NaN (0x7fc00000) if any c_k is NaN.  Else med is the median
+ *   above and d_k = |c_k - med|: one separately rounded fp32 subtraction with the
+ *   sign bit cleared; a NaN distance (inf - inf) becomes 0x7fc00000.  The unsigned
+ *   bit pattern of d_k is its key: 0 < ... < +inf < NaN, both zeros are key 0.
+ *   T is the key of rank b-1, ascending.  Every row with key < T is kept, and the
+ *   rows with key == T in table order until b rows are kept ("lowest table
+ *   position"; the reference's argsort is not stable, so which of two equally
+ *   distant values it keeps is an accident: a documented divergence).  acc = +0;
+ *   for the kept rows in table order acc = acc + c_k, each add rounded in fp32;
+ *   the result is acc / (float)b by IEEE division.  Only the set of kept values
+ *   enters, not their order by distance: torch.mean's blocked sum differs from
+ *   this sequential one by rounding only.  With trim == 0 the result is bit for
+ *   bit that of plato_agg_mean_rows on the same table.
  *   d_x_f32  device array of K pointers, each to n_f32 fp32 values
  *   d_x_i64  device array of K pointers to n_i64 int64 values, or NULL when
  *            n_i64 == 0
- *   trim     reserved for trimmed modes (0 <= 2*trim < K); the median ignores it
+ *   trim     0 <= 2*trim < K in both modes; the median ignores it otherwise
  *   d_out_f32 (16-byte aligned), d_out_i64_as_f32: the results
- * 1 <= K <= PLATO_AGG_ROBUST_MAX_K.
+ * 1 <= K <= PLATO_AGG_ROBUST_MAX_K.  Any other mode is PLATO_AGG_EINVAL.
  */
 #define PLATO_AGG_ROBUST_MEDIAN 0
+#define PLATO_AGG_ROBUST_NEAREST_MEAN 1
 #define PLATO_AGG_ROBUST_MAX_K 256
 int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
                              int trim, float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32, size_t n_i64,
@@ -572,7 +595,10 @@ int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_
  * Multi-Krum (examples/detector/aggregations.py:176-230, "Multi-krum" of
  * server.secure_aggregation_type): the K x K squared L2 distances over the whole
  * flattened model, a selection on the host (plato_amd/krum.py), and the mean of
- * the selected rows.  "Krum" and "Bulyan" are not provided.
+ * the selected rows.  "Bulyan" (aggregations.py:76-144) is the same distances,
+ * its own selection on the host (plato_amd/krum.py: bulyan_select) and
+ * plato_agg_robust_columns(PLATO_AGG_ROBUST_NEAREST_MEAN) over the selected rows.
+ * "Krum" is not provided.
  *
  * plato_agg_pairwise_sqdist  <- the distance loop of every selection step
  *                               (aggregations.py:185-192):

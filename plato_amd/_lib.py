@@ -28,7 +28,7 @@ PLATO_AGG_PORT_CAST_FIRST = 1
 PLATO_AGG_SEG_NEG_DIV = 1
 PLATO_AGG_FEDADP_TABLES_READY = 1
 PLATO_AGG_DECODE = {"native": 0, "bf16": 1, "qsgd": 2}
-PLATO_AGG_ROBUST = {"median": 0}
+PLATO_AGG_ROBUST = {"median": 0, "nearest_mean": 1}
 PLATO_AGG_ROBUST_MAX_K = 256
 PLATO_AGG_PAIRDIST_CHAIN = 128
 

@@ -479,8 +479,10 @@ class FedAvgEngine:
                          trim: int = 0) -> "OrderedDict[str, torch.Tensor]":
         """The detector example's order-statistic aggregators over K native payloads, on the GPU.
 
-        ``mode="median"``: the coordinate-wise lower median (``aggregations.median``).  Returns CPU
-        float32 tensors for every entry, the int64 counters included, as the reference does.
+        ``mode="median"``: the coordinate-wise lower median (``aggregations.median``).
+        ``mode="nearest_mean"``: the mean of the ``K - 2 * trim`` values nearest that median
+        (``aggregations.trimmed_mean``, whose own ``num_attackers`` is 0).  Returns CPU float32 tensors
+        for every entry, the int64 counters included, as the reference does.
         """
         k = len(payloads)
         if k == 0:
@@ -503,13 +505,38 @@ class FedAvgEngine:
         """The detector example's ``Multi-krum`` (``aggregations.multi_krum``) over K native payloads, on
         the GPU: the mean of the ``K - 2f - 2`` clients its distance scores select.  Returns CPU float32
         tensors for every entry, the int64 counters included, as the reference does."""
+        if 0 < len(payloads) <= 2 * int(f) + 2:
+            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, "
+                             f"got {len(payloads)}")
+        rnd = self._stage_selected(payloads)
+        rnd.launch_multi_krum(f)
+        self.last_selected = rnd.selected
+        return rnd.result()
+
+    def aggregate_bulyan(self, payloads: Sequence[Mapping[str, torch.Tensor]], f: int
+                         ) -> "OrderedDict[str, torch.Tensor]":
+        """The detector example's ``Bulyan`` (``aggregations.bulyan``) over K native payloads, on the GPU:
+        its distance scores select theta = min(K - 2f, K - 2 - f) clients, and every coordinate is the
+        mean of the theta - 2f selected values nearest their median.  K, the reference's
+        ``clients.total_clients``, is the number of payloads.  Returns CPU float32 tensors for every
+        entry, the int64 counters included, as the reference does."""
+        from .krum import bulyan_min_clients
+
+        if payloads and (int(f) < 0 or len(payloads) < bulyan_min_clients(f)):
+            raise ValueError(f"Bulyan with f = {int(f)} needs at least {bulyan_min_clients(max(int(f), 0))} clients, "
+                             f"got {len(payloads)}")
+        rnd = self._stage_selected(payloads)
+        rnd.launch_bulyan(f)
+        self.last_selected = rnd.selected
+        return rnd.result()
+
+    def _stage_selected(self, payloads: Sequence[Mapping[str, torch.Tensor]]) -> "AggregationRound":
+        """A round with K native payloads staged as weights, for the distance-based aggregators."""
         k = len(payloads)
         if k == 0:
             raise ValueError("no client payloads to aggregate")
         if k > _lib.PLATO_AGG_ROBUST_MAX_K:
             raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, got {k}")
-        if k <= 2 * int(f) + 2:
-            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, got {k}")
         codec = payload_codec(payloads[0])
         if codec != "native":
             raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
@@ -518,9 +545,7 @@ class FedAvgEngine:
         for i, sd in enumerate(payloads):
             if not rnd.adopt(i, sd):
                 rnd.put_client(i, sd)
-        rnd.launch_multi_krum(f)
-        self.last_selected = rnd.selected
-        return rnd.result()
+        return rnd
 
     def aggregate_deltas(self, deltas_received: Sequence[Mapping[str, torch.Tensor]],
                          weights: Sequence[float], scales: Sequence[float] | None = None
@@ -932,8 +957,11 @@ class AggregationRound:
 
         ``mode="median"`` is ``aggregations.median`` of the reference's detector example
         (examples/detector/aggregations.py): ``torch.median(dim=0)`` of the flattened models, the
-        lower median per coordinate.  No baseline is read.  Every entry of the result is float32,
-        the int64 counters included (``flatten_weights`` promotes them).
+        lower median per coordinate.  ``mode="nearest_mean"`` is ``aggregations.trimmed_mean``: per
+        coordinate the mean of the ``K - 2 * trim`` values nearest that median, equally distant ones
+        taken in table order (``0 <= 2 * trim < K``; the reference's own ``num_attackers`` is 0).  No
+        baseline is read.  Every entry of the result is float32, the int64 counters included
+        (``flatten_weights`` promotes them).
         """
         if mode not in _lib.PLATO_AGG_ROBUST:
             raise ValueError(f"unknown robust aggregation mode {mode!r} (supported: {sorted(_lib.PLATO_AGG_ROBUST)})")
@@ -1017,9 +1045,51 @@ class AggregationRound:
         float32, the int64 counters included."""
         from .krum import multi_krum_select
 
-        slots, tf, ti, stream = self._distance_rows("launch_multi_krum", order)
-        if len(slots) <= 2 * int(f) + 2:
-            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, got {len(slots)}")
+        f = int(f)
+
+        def check(k):
+            if k <= 2 * f + 2:
+                raise ValueError(f"Multi-Krum with f = {f} needs more than {2 * f + 2} clients, got {k}")
+
+        def mean(sf, si, m, out_f, out_i, stream):
+            lay = self.layout
+            with self._timed("mean_rows", stream):
+                _lib.call("plato_agg_mean_rows", _ptr(sf), _ptr(si) if lay.n_i64 else None, m, _ptr(out_f),
+                          _ptr(out_i) if lay.n_i64 else None, lay.n_f32, lay.n_i64, _stream_handle(stream))
+
+        self._launch_selected("launch_multi_krum", order, check, lambda dist: multi_krum_select(dist, f), mean)
+
+    def launch_bulyan(self, f: int, order: Sequence[int] | None = None) -> None:
+        """``aggregations.bulyan`` of the reference's detector example over the staged client rows: the
+        distance matrix on the device, the selection of theta = min(K - 2f, K - 2 - f) clients on the
+        host (``plato_amd.krum.bulyan_select``), then per coordinate the mean of the theta - 2f selected
+        values nearest their median (``plato_agg_robust_columns``, nearest-mean mode, over the selected
+        rows in selection order).  ``self.selected`` holds the selected client slots in selection order.
+        No baseline is read; every entry of the result is float32, the int64 counters included."""
+        from .krum import bulyan_min_clients, bulyan_select
+
+        f = int(f)
+
+        def check(k):
+            if f < 0 or k < bulyan_min_clients(f):
+                raise ValueError(f"Bulyan with f = {f} needs at least {bulyan_min_clients(max(f, 0))} clients, got {k}")
+
+        def nearest_mean(sf, si, m, out_f, out_i, stream):
+            lay = self.layout
+            with self._timed("robust_nearest_mean", stream):
+                _lib.call("plato_agg_robust_columns", _lib.PLATO_AGG_ROBUST["nearest_mean"], _ptr(sf),
+                          _ptr(si) if lay.n_i64 else None, m, f, _ptr(out_f), _ptr(out_i) if lay.n_i64 else None,
+                          lay.n_f32, lay.n_i64, _stream_handle(stream))
+
+        self._launch_selected("launch_bulyan", order, check, lambda dist: bulyan_select(dist, f), nearest_mean)
+
+    def _launch_selected(self, what: str, order, check, select, combine) -> None:
+        """The distance-based aggregators' common path: ``check(K)`` refuses a K too small, the distance
+        matrix is computed on the device, ``select(dist)`` picks rows on the host, and
+        ``combine(sf, si, m, out_f, out_i, stream)`` launches the kernel that turns the pointer tables of
+        the m selected rows, in selection order, into the result."""
+        slots, tf, ti, stream = self._distance_rows(what, order)
+        check(len(slots))
         eng, lay = self.engine, self.layout
         self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
         self._k = len(slots)
@@ -1027,18 +1097,15 @@ class AggregationRound:
         e0.record(stream)
         dist = self._pairwise_sqdist(len(slots), tf, ti, stream)
         t0 = time.perf_counter()
-        picks = multi_krum_select(dist, f)
+        picks = select(dist)
         self.timings["select_ms"] = (time.perf_counter() - t0) * 1e3
-        self.selected = [slots[p] for p in picks]
+        self.selected = eng.last_selected = [slots[p] for p in picks]
         self._k = len(slots) + len(picks)  # algorithmic_bytes: K rows for the distances, then the selected ones again
         sf, si = eng._pointer_tables(np.asarray([self._pf[i] for i in self.selected], dtype=np.int64),
                                      np.asarray([self._pi[i] for i in self.selected], dtype=np.int64))
         out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
         out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        n_i = lay.n_i64
-        with self._timed("mean_rows", stream):
-            _lib.call("plato_agg_mean_rows", _ptr(sf), _ptr(si) if n_i else None, len(picks), _ptr(out_f),
-                      _ptr(out_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
+        combine(sf, si, len(picks), out_f, out_i, stream)
         e1.record(stream)
         self._kernel_events = (e0, e1)
         self._robust = True

@@ -445,6 +445,9 @@ class MultiDeviceEngine:
     def aggregate_multi_krum(self, payloads, f: int = 2):
         raise NotImplementedError("robust aggregation (Multi-Krum) runs on one GPU: use FedAvgEngine")
 
+    def aggregate_bulyan(self, payloads, f: int):
+        raise NotImplementedError("robust aggregation (Bulyan) runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""
@@ -457,6 +460,9 @@ class MultiRound:
 
     def launch_multi_krum(self, f: int = 2, order=None):
         raise NotImplementedError("robust aggregation (Multi-Krum) runs on one GPU: use FedAvgEngine")
+
+    def launch_bulyan(self, f: int, order=None):
+        raise NotImplementedError("robust aggregation (Bulyan) runs on one GPU: use FedAvgEngine")
 
     def __init__(self, engine: MultiDeviceEngine, layout: ArenaLayout, capacity: int, codec: str):
         self.engine = engine

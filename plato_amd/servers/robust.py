@@ -5,7 +5,10 @@
 coordinate-wise order statistic over the received models, not a weighted sum; here it runs on the GPU
 (``plato_agg_robust_columns``).  Its ``Multi-krum`` scores every client by its squared distances to the
 others and averages the selected ones: distances and mean on the GPU (``plato_agg_pairwise_sqdist``,
-``plato_agg_mean_rows``), the selection on the host (``plato_amd.krum``).  The detector server's
+``plato_agg_mean_rows``), the selection on the host (``plato_amd.krum``).  Its ``Trimmed-mean`` and
+``Bulyan`` end in the mean of the values nearest the coordinate-wise median (the nearest-mean mode of
+``plato_agg_robust_columns``), ``Bulyan`` after a selection of Multi-krum's kind; they are
+:class:`DetectorAggregationMixin`'s, which hands every other name to its parent.  The detector server's
 ``weights_received`` pipeline (attack simulation, filters) is the base class's and runs before this
 hook, unchanged::
 
@@ -74,6 +77,71 @@ class RobustAggregationMixin(FusedAggregationMixin):
                     rnd.launch_multi_krum(MULTI_KRUM[name])
                 else:
                     rnd.launch_robust(ROBUST_MODES[name])
+            with tracing.range("plato_amd.fetch"):
+                return await self._finish(rnd)
+        finally:
+            engine.release_arrivals()
+
+
+#: the names :class:`DetectorAggregationMixin` handles itself
+DETECTOR_MODES = ("Bulyan", "Trimmed-mean")
+
+
+def _num_attackers() -> int:
+    """``len(Config().clients.attacker_ids)``, as ``aggregations.bulyan`` reads it (aggregations.py:80)."""
+    from plato.config import Config
+
+    return len(Config().clients.attacker_ids)
+
+
+class DetectorAggregationMixin(RobustAggregationMixin):
+    """``RobustAggregationMixin`` plus the detector example's "Bulyan" and "Trimmed-mean"; every other
+    name is the parent's.
+
+    "Bulyan" (aggregations.py:76-144): f is ``num_attackers`` if set, else
+    ``len(Config().clients.attacker_ids)`` as in the reference.  K is the number of payloads received,
+    where the reference reads ``clients.total_clients``: the two agree whenever every client reports,
+    the only case in which the reference's loop is coherent (with fewer payloads than total_clients its
+    cluster can outgrow the clients that remain).
+
+    "Trimmed-mean" (aggregations.py:233-255): per coordinate the mean of the ``K - 2 * trim`` values
+    nearest the median; ``trim`` defaults to 0, the reference's hard-coded ``num_attackers = 0``.
+    """
+
+    #: None = ``len(Config().clients.attacker_ids)``
+    num_attackers = None
+    trim = 0
+
+    async def aggregate_weights(self, updates, baseline_weights, weights_received):
+        name = self.robust_aggregation_type()
+        if name not in DETECTOR_MODES:
+            if name is not None and name not in ROBUST_MODES and name not in MULTI_KRUM:  # the parent's refusal, this list
+                raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
+                                 f"(supported: {', '.join(sorted({*ROBUST_MODES, *MULTI_KRUM, *DETECTOR_MODES}))})")
+            return await super().aggregate_weights(updates, baseline_weights, weights_received)
+        codec = payload_codec(weights_received[0])
+        if codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
+        engine = self.aggregation_engine()
+        if getattr(engine, "primary", None) is not None:
+            raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
+        if name == "Bulyan":
+            f = int(self.num_attackers) if self.num_attackers is not None else _num_attackers()
+        try:
+            rnd = engine.begin(weights_received[0], len(weights_received))
+
+            def stage():
+                with tracing.range("plato_amd.stage"):
+                    for slot, payload in enumerate(weights_received):
+                        if not rnd.adopt(slot, payload):
+                            rnd.put_client(slot, payload)
+
+            await self._off_loop(stage)
+            with tracing.range("plato_amd.launch"):
+                if name == "Bulyan":
+                    rnd.launch_bulyan(f)
+                else:
+                    rnd.launch_robust("nearest_mean", int(self.trim))
             with tracing.range("plato_amd.fetch"):
                 return await self._finish(rnd)
         finally:
