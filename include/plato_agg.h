@@ -72,6 +72,11 @@
  *   plato_agg_mean_rows           loop of every selection step and the mean of the
  *                                 selected models (aggregations.py:176-230); the
  *                                 distances serve Bulyan's selection too (:86-123)
+ *   plato_agg_trust_stats,     <- the detector example's Fl-trust: the torch.dot /
+ *   plato_agg_scaled_sum          torch.norm loop over the clients (aggregations.py:
+ *                                 413-423, :432-433) and the scaled candidates and
+ *                                 their torch.sum (:428-441); torch.mean (:408) is
+ *                                 plato_agg_mean_rows
  */
 #ifndef PLATO_AGG_H
 #define PLATO_AGG_H
@@ -651,6 +656,74 @@ int plato_agg_pairwise_sqdist(const float* const* d_x_f32, const int64_t* const*
 int plato_agg_mean_rows(const float* const* d_x_f32, const int64_t* const* d_x_i64, int m,
                         float* d_out_f32, float* d_out_i64_as_f32,
                         size_t n_f32, size_t n_i64, hipStream_t stream);
+
+/*
+ * Fl-trust (examples/detector/aggregations.py:403-453, "Fl-trust" of
+ * server.secure_aggregation_type): the cosine of every client with the mean model,
+ * clipped at 0 and normalised, weighs the clients, each rescaled to the mean's
+ * norm.  With X the [K, D] matrix of flatten_weights (counters promoted to fp32):
+ *   m     = torch.mean(X, dim=0)                           plato_agg_mean_rows
+ *   cos_k = dot(x_k, m) / (|m| + 1e-9) / (|x_k| + 1e-9)    plato_agg_trust_stats, then
+ *   w_k   = max(cos_k, 0) / (sum(max(cos, 0)) + 1e-9)      the host (plato_amd/trust.py)
+ *   out   = sum_k x_k * w_k / |x_k + 1e-9| * |m|           plato_agg_scaled_sum
+ *
+ * plato_agg_trust_stats  <- torch.dot(weight, model_re), torch.norm(weight),
+ *                           torch.norm(weight + 1e-9), torch.norm(model_re)
+ *   With c_k[e] = x_k[e] in the fp32 region and (float)x_k[e] (round to nearest
+ *   even) in the int64 region, and r[e] the reference vector (fp32 in both regions;
+ *   for Fl-trust the output of plato_agg_mean_rows over the same table):
+ *     d_out[k]      = sum over e of c_k[e] * r[e]
+ *     d_out[K+k]    = sum over e of c_k[e]^2
+ *     d_out[2K+k]   = sum over e of fp32(c_k[e] + eps)^2   (one fp32 addition)
+ *     d_out[3K]     = sum over e of r[e]^2
+ *   Every product is formed in float64 from its fp32 operands (exact: 24 + 24
+ *   bits) and added in float64 in a fixed order: per lane over the coordinates of
+ *   a chunk, across the lanes of a wave, across the waves of a workgroup, then
+ *   over the chunks (through d_workspace, by a final kernel, in chunk order).  A
+ *   region's chunk length is a multiple of PLATO_AGG_TRUST_TILE chosen by its
+ *   coordinate count alone.  No atomics.
+ *   Properties: (a) bitwise repeatable from run to run; (b) client k's three
+ *   values depend only on row k, on r and on (n_f32, n_i64), not on K or on the
+ *   order of the pointer table: a permuted table gives the bitwise permuted output;
+ *   (c) each value is within D * 2^-53 * sum|terms| of the exact sum, D = n_f32 +
+ *   n_i64; (d) NaN and +-inf propagate by IEEE rules.
+ *   d_x_f32, d_x_i64   device arrays of K row pointers (d_x_i64 NULL when n_i64 == 0)
+ *   d_ref_f32, d_ref_i64_as_f32  the reference vector's two regions, fp32
+ *   d_workspace        plato_agg_trust_stats_workspace(K, n_f32, n_i64) bytes
+ *                      (0: bad arguments), 256-byte aligned
+ *   d_out              3K + 1 doubles, 16-byte aligned
+ *   1 <= K <= PLATO_AGG_ROBUST_MAX_K; fewer than 2^38 coordinates per region;
+ *   n_f32 == n_i64 == 0 is a success that launches nothing and writes nothing.
+ *
+ * plato_agg_scaled_sum  <- candidate = weight * w / torch.norm(weight + 1e-9) *
+ *                          torch.norm(model_re); torch.sum(candidates, dim=0)
+ *   for every coordinate e: acc = +0; for k = 0..K-1 in table order:
+ *     t = c_k[e] * d_mul[k]; t = t / d_div[k] (IEEE division); t = t * post;
+ *     acc = acc + t
+ *   each operation fp32 and separately rounded, as ATen evaluates `x * w / n * nm`
+ *   with 0-dim fp32 tensors.  No row is skipped: 0 * inf is NaN, as in the
+ *   reference.  fp32 results for both regions.  d_mul and d_div are device arrays
+ *   of K floats.  Same limits as plato_agg_mean_rows.
+ *
+ * Documented divergences from the reference, all by rounding or range only:
+ *   - the mean and the final sum are sequential over the rows; ATen's torch.mean
+ *     and torch.sum(dim=0) are blocked, equal to the sequential sum only for
+ *     small K (any-order summation bound, as for plato_agg_mean_rows);
+ *   - dots and norms are float64 sums; the reference's are fp32 (BLAS sdot and
+ *     ATen's norm), whose own error grows with D;
+ *   - the square root is taken in float64 (plato_amd/trust.py): a squared norm
+ *     above the fp32 maximum gives a finite norm where the reference gives inf.
+ */
+#define PLATO_AGG_TRUST_TILE 1024
+size_t plato_agg_trust_stats_workspace(int K, size_t n_f32, size_t n_i64);
+int plato_agg_trust_stats(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                          const float* d_ref_f32, const float* d_ref_i64_as_f32, float eps,
+                          size_t n_f32, size_t n_i64, void* d_workspace,
+                          double* d_out /* 3K + 1 */, hipStream_t stream);
+int plato_agg_scaled_sum(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                         const float* d_mul /* K */, const float* d_div /* K */, float post,
+                         float* d_out_f32, float* d_out_i64_as_f32,
+                         size_t n_f32, size_t n_i64, hipStream_t stream);
 
 /*
  * Single-process RCCL communicator over the GPUs one Plato server drives.

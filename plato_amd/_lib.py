@@ -31,6 +31,7 @@ PLATO_AGG_DECODE = {"native": 0, "bf16": 1, "qsgd": 2}
 PLATO_AGG_ROBUST = {"median": 0, "nearest_mean": 1}
 PLATO_AGG_ROBUST_MAX_K = 256
 PLATO_AGG_PAIRDIST_CHAIN = 128
+PLATO_AGG_TRUST_TILE = 1024
 
 _c_void_p = ctypes.c_void_p
 _c_size_t = ctypes.c_size_t
@@ -171,6 +172,13 @@ SIGNATURES = {
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_size_t, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "plato_agg_mean_rows": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
+    "plato_agg_trust_stats_workspace": (_c_size_t, [_c_int, _c_size_t, _c_size_t]),
+    "plato_agg_trust_stats": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_float, _c_size_t, _c_size_t, _c_void_p,
+                 _c_void_p, _c_void_p]),
+    "plato_agg_scaled_sum": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_size_t,
+                 _c_size_t, _c_void_p]),
     "plato_agg_comm_create": (_c_int, [_c_int, _c_void_p, ctypes.POINTER(_c_void_p)]),
     "plato_agg_comm_destroy": (_c_int, [_c_void_p]),
     "plato_agg_comm_size": (_c_int, [_c_void_p]),

@@ -530,6 +530,16 @@ class FedAvgEngine:
         self.last_selected = rnd.selected
         return rnd.result()
 
+    def aggregate_fltrust(self, payloads: Sequence[Mapping[str, torch.Tensor]]
+                          ) -> "OrderedDict[str, torch.Tensor]":
+        """The detector example's ``Fl-trust`` (``aggregations.fl_trust``) over K native payloads, on the
+        GPU: every client weighed by its clipped cosine with the mean model and rescaled to the mean's
+        norm.  ``self.last_trust`` holds the scalars (``plato_amd.trust.fltrust_weights``).  Returns CPU
+        float32 tensors for every entry, the int64 counters included, as the reference does."""
+        rnd = self._stage_selected(payloads)
+        rnd.launch_fltrust()
+        return rnd.result()
+
     def _stage_selected(self, payloads: Sequence[Mapping[str, torch.Tensor]]) -> "AggregationRound":
         """A round with K native payloads staged as weights, for the distance-based aggregators."""
         k = len(payloads)
@@ -1082,6 +1092,51 @@ class AggregationRound:
                           lay.n_f32, lay.n_i64, _stream_handle(stream))
 
         self._launch_selected("launch_bulyan", order, check, lambda dist: bulyan_select(dist, f), nearest_mean)
+
+    def launch_fltrust(self, order: Sequence[int] | None = None) -> None:
+        """``aggregations.fl_trust`` of the reference's detector example over the staged client rows: the
+        sequential mean of the rows (``plato_agg_mean_rows``), every client's dot with it and the norms
+        in one pass (``plato_agg_trust_stats``), the cosines, their clip and normalisation on the host
+        (``plato_amd.trust.fltrust_weights``, after a blocking read of the ``3K + 1`` sums), then the sum
+        of the rows scaled by ``w_k / |x_k + 1e-9| * |mean|`` in table order (``plato_agg_scaled_sum``).
+        ``self.trust`` holds the scalars.  No baseline is read; every entry of the result is float32,
+        the int64 counters included."""
+        from .trust import EPS, fltrust_weights
+
+        slots, tf, ti, stream = self._distance_rows("launch_fltrust", order)
+        eng, lay = self.engine, self.layout
+        k, n_i = len(slots), lay.n_i64
+        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
+        self._k = 3 * k  # algorithmic_bytes: the rows are read by the mean, the statistics and the sum
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        mean_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
+        mean_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
+        with self._timed("mean_rows", stream):
+            _lib.call("plato_agg_mean_rows", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(mean_f),
+                      _ptr(mean_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
+        nbytes = _lib.lib().plato_agg_trust_stats_workspace(k, lay.n_f32, n_i)
+        work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=eng.device)
+        stats = torch.empty(3 * k + 1, dtype=torch.float64, device=eng.device)
+        with self._timed("trust_stats", stream):
+            _lib.call("plato_agg_trust_stats", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(mean_f),
+                      _ptr(mean_i) if n_i else None, EPS, lay.n_f32, n_i, _ptr(work), _ptr(stats),
+                      _stream_handle(stream))
+        host_stats = stats.cpu().numpy()  # stream-ordered, blocking: the scalars are formed on the host
+        t0 = time.perf_counter()
+        self.trust = eng.last_trust = fltrust_weights(host_stats, k, EPS)
+        self.timings["trust_scalars_ms"] = (time.perf_counter() - t0) * 1e3
+        scal = torch.from_numpy(np.concatenate([self.trust["weights"], self.trust["div"]])).to(eng.device)
+        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
+        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
+        with self._timed("trust_combine", stream):
+            _lib.call("plato_agg_scaled_sum", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(scal),
+                      scal.data_ptr() + 4 * k, float(self.trust["nm"]), _ptr(out_f), _ptr(out_i) if n_i else None,
+                      lay.n_f32, n_i, _stream_handle(stream))
+        e1.record(stream)
+        self._kernel_events = (e0, e1)
+        self._robust = True
+        self._fetch(stream, out_f, out_i, (tf, ti, mean_f, mean_i, work, stats, scal))
 
     def _launch_selected(self, what: str, order, check, select, combine) -> None:
         """The distance-based aggregators' common path: ``check(K)`` refuses a K too small, the distance

@@ -448,6 +448,9 @@ class MultiDeviceEngine:
     def aggregate_bulyan(self, payloads, f: int):
         raise NotImplementedError("robust aggregation (Bulyan) runs on one GPU: use FedAvgEngine")
 
+    def aggregate_fltrust(self, payloads):
+        raise NotImplementedError("robust aggregation (Fl-trust) runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""
@@ -463,6 +466,9 @@ class MultiRound:
 
     def launch_bulyan(self, f: int, order=None):
         raise NotImplementedError("robust aggregation (Bulyan) runs on one GPU: use FedAvgEngine")
+
+    def launch_fltrust(self, order=None):
+        raise NotImplementedError("robust aggregation (Fl-trust) runs on one GPU: use FedAvgEngine")
 
     def __init__(self, engine: MultiDeviceEngine, layout: ArenaLayout, capacity: int, codec: str):
         self.engine = engine

@@ -8,7 +8,10 @@ others and averages the selected ones: distances and mean on the GPU (``plato_ag
 ``plato_agg_mean_rows``), the selection on the host (``plato_amd.krum``).  Its ``Trimmed-mean`` and
 ``Bulyan`` end in the mean of the values nearest the coordinate-wise median (the nearest-mean mode of
 ``plato_agg_robust_columns``), ``Bulyan`` after a selection of Multi-krum's kind; they are
-:class:`DetectorAggregationMixin`'s, which hands every other name to its parent.  The detector server's
+:class:`DetectorAggregationMixin`'s, which hands every other name to its parent.  Its ``Fl-trust`` weighs
+every client by its clipped cosine with the mean model (``plato_agg_mean_rows``,
+``plato_agg_trust_stats``, the scalars on the host in ``plato_amd.trust``, ``plato_agg_scaled_sum``); it is
+:class:`TrustAggregationMixin`'s, which again hands every other name to its parent.  The detector server's
 ``weights_received`` pipeline (attack simulation, filters) is the base class's and runs before this
 hook, unchanged::
 
@@ -142,6 +145,48 @@ class DetectorAggregationMixin(RobustAggregationMixin):
                     rnd.launch_bulyan(f)
                 else:
                     rnd.launch_robust("nearest_mean", int(self.trim))
+            with tracing.range("plato_amd.fetch"):
+                return await self._finish(rnd)
+        finally:
+            engine.release_arrivals()
+
+
+#: the name :class:`TrustAggregationMixin` handles itself
+TRUST_MODES = ("Fl-trust",)
+
+
+class TrustAggregationMixin(DetectorAggregationMixin):
+    """``DetectorAggregationMixin`` plus the detector example's "Fl-trust" (aggregations.py:403-453);
+    every other name is the parent's.  With it every working aggregator of that example runs on the GPU
+    ("Krum" and "Afa" have no behaviour to match: INTEGRATION.md §12)."""
+
+    async def aggregate_weights(self, updates, baseline_weights, weights_received):
+        name = self.robust_aggregation_type()
+        if name not in TRUST_MODES:
+            if (name is not None and name not in ROBUST_MODES and name not in MULTI_KRUM
+                    and name not in DETECTOR_MODES):  # the parents' refusal, this list
+                supported = sorted({*ROBUST_MODES, *MULTI_KRUM, *DETECTOR_MODES, *TRUST_MODES})
+                raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
+                                 f"(supported: {', '.join(supported)})")
+            return await super().aggregate_weights(updates, baseline_weights, weights_received)
+        codec = payload_codec(weights_received[0])
+        if codec != "native":
+            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
+        engine = self.aggregation_engine()
+        if getattr(engine, "primary", None) is not None:
+            raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
+        try:
+            rnd = engine.begin(weights_received[0], len(weights_received))
+
+            def stage():
+                with tracing.range("plato_amd.stage"):
+                    for slot, payload in enumerate(weights_received):
+                        if not rnd.adopt(slot, payload):
+                            rnd.put_client(slot, payload)
+
+            await self._off_loop(stage)
+            with tracing.range("plato_amd.launch"):
+                rnd.launch_fltrust()
             with tracing.range("plato_amd.fetch"):
                 return await self._finish(rnd)
         finally:
