@@ -104,7 +104,11 @@ int plato_agg_tune_sdot_shared(int variant, const float* d_x, const float* const
  * rounds 2-3 default), 2-4 = timing probes of variant 1 (NOT the FedAvg: no code loads / no table
  * lookups / neither), 5 = 1024x8x8 plain form of round 1, 6 = variant 0 at 256 threads.
  * plato_agg_tune_qsgd_chunk gives the chunk capacity (elements per workgroup pass) the variant is
- * built for. */
+ * built for.  The variants that decode by a float64 reciprocal product (7-12 arithmetic decode;
+ * 24, 25, 27-30, 32-42 fast tables) return PLATO_AGG_EINVAL for a divisor the product is not the
+ * exact division for, an even integer that is no power of two (csrc/common.h recip_product_exact);
+ * plato_agg_fedavg_qsgd runs variant 31's IEEE tables there.  plato_agg_tune_fedadp_dots refuses
+ * its float64-product variants an lr of that kind in the same way. */
 int plato_agg_tune_num_qsgd_variants(void);
 int plato_agg_tune_qsgd_chunk(int variant);
 int plato_agg_tune_fedavg_qsgd(int variant, const uint8_t* const* d_codes_f32, const uint8_t* const* d_codes_i64,

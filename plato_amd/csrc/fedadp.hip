@@ -121,10 +121,12 @@ __device__ __forceinline__ float adp_i64(int64_t x, int64_t b, bool neg, float l
 }
 
 // (-d) / lr, correctly rounded, as RN32(RN64(-d * RN64(1 / lr))): the float64 product is within
-// 2^-52 (relative) of the quotient, while a quotient of two floats that is not a float lies at
-// least 2^-49 (relative) from every midpoint of the float grid (and is never on one), so the one
-// rounding to float gives the float32 division's bits (tests/test_division.py) — 3 instructions
-// instead of the division's ~10
+// 2^-52 (relative) of the quotient, while a quotient of two floats that is not on a midpoint of the
+// float grid lies at least 2^-49 (relative) from every midpoint, so the one rounding to float gives
+// the float32 division's bits (tests/test_division.py) — 3 instructions instead of the division's
+// ~10.  A quotient exactly on a midpoint (between two subnormals) exists only when lr is an even
+// integer that is no power of two (common.h recip_product_exact); the product can round such a tie
+// the other way, so those lr (none below 2) run the shapes without kFDiv64 (adp_for_lr, run_fedadp)
 __device__ __forceinline__ float adp_div_lr_f64(float v, double inv_lr) { return float(double(v) * inv_lr); }
 
 // The last segment with flat_offset <= p (segments are in flat order).
@@ -602,6 +604,7 @@ struct AdpLaunch {
   void (*fn)(const AdpArgs&, hipStream_t);
   bool uses_xb;
   bool delta;  // kFDelta: for delta arenas (null baseline)
+  bool recip;  // kFDiv64: exact only for an lr that recip_product_exact (common.h) accepts
 };
 
 template <int kS, int kW, int kIt, int kD, int kF, int kProbe>
@@ -612,7 +615,8 @@ void launch_adp_impl(const AdpArgs& a, hipStream_t st) {
 
 template <int kS, int kW, int kIt, int kD, int kF, int kProbe = 0>
 constexpr AdpLaunch adp_launch() {
-  return AdpLaunch{&launch_adp_impl<kS, kW, kIt, kD, kF, kProbe>, (kF & kFXB) != 0, (kF & kFDelta) != 0};
+  return AdpLaunch{&launch_adp_impl<kS, kW, kIt, kD, kF, kProbe>, (kF & kFXB) != 0, (kF & kFDelta) != 0,
+                   (kF & kFDiv64) != 0};
 }
 
 // The product's shape: 192-step stages of 12 producer waves x 2 iterations, x and b from the
@@ -625,6 +629,14 @@ constexpr AdpLaunch kAdpDefault = adp_launch<192, 12, 2, 2, kFYnt | kFDiv64 | kF
 // registers the b loads held): 1.077 / 1.080 against 1.088 / 1.092 ms with two, interleaved on two leases
 // (profiles/r05zzu_delta_probe_shapes.log, r05zzm_delta_probe.log; 1.054 by rocprof with two, r05zzo)
 constexpr AdpLaunch kAdpDefaultDelta = adp_launch<192, 12, 2, 3, kFYnt | kFDiv64 | kFXB | kFDelta>();
+// The same two shapes with the IEEE division, for an lr the float64 product is not exact for
+constexpr AdpLaunch kAdpDefaultIeee = adp_launch<192, 12, 2, 2, kFYnt | kFXB>();
+constexpr AdpLaunch kAdpDefaultDeltaIeee = adp_launch<192, 12, 2, 3, kFYnt | kFXB | kFDelta>();
+// The product's kernel for a call: by the arenas (weights or deltas) and by lr (every |lr| < 2 is exact)
+const AdpLaunch& adp_for_lr(bool delta, float lr) {
+  if (plato_agg_internal::recip_product_exact(lr)) return delta ? kAdpDefaultDelta : kAdpDefault;
+  return delta ? kAdpDefaultDeltaIeee : kAdpDefaultIeee;
+}
 #ifdef PLATO_AGG_TUNE
 const AdpLaunch kAdpVariants[] = {
     kAdpDefault,                                            // 0: the default
@@ -699,7 +711,7 @@ int plato_agg_fedadp_dots(const float* d_x, const void* const* d_src_f32, const 
                           const float* d_base_f32, const int64_t* d_base_i64, const plato_agg_segment* d_segs,
                           uint32_t n_segs, size_t n_flat, size_t n_f32, size_t n_i64, float lr, int with_xx, void* d_workspace,
                           float* d_out_xy, float* d_out_yy, hipStream_t stream) {
-  return run_fedadp(d_base_f32 ? kAdpDefault : kAdpDefaultDelta, d_x, d_src_f32, d_src_i64, n_pairs, d_base_f32,
+  return run_fedadp(adp_for_lr(d_base_f32 == nullptr, lr), d_x, d_src_f32, d_src_i64, n_pairs, d_base_f32,
                     d_base_i64, d_segs, n_segs, n_flat, n_f32, n_i64, lr, with_xx, d_workspace, d_out_xy, d_out_yy,
                     stream, 0);
 }
@@ -710,7 +722,7 @@ int plato_agg_fedadp_dots_ex(const float* d_x, const void* const* d_src_f32, con
                              size_t n_i64, float lr, int with_xx, void* d_workspace, float* d_out_xy, float* d_out_yy,
                              hipStream_t stream, int flags) {
   if (flags & ~PLATO_AGG_FEDADP_TABLES_READY) return set_error(PLATO_AGG_EINVAL, "unknown fedadp_dots flags");
-  return run_fedadp(d_base_f32 ? kAdpDefault : kAdpDefaultDelta, d_x, d_src_f32, d_src_i64, n_pairs, d_base_f32,
+  return run_fedadp(adp_for_lr(d_base_f32 == nullptr, lr), d_x, d_src_f32, d_src_i64, n_pairs, d_base_f32,
                     d_base_i64, d_segs, n_segs, n_flat, n_f32, n_i64, lr, with_xx, d_workspace, d_out_xy, d_out_yy,
                     stream, flags);
 }
@@ -756,6 +768,11 @@ int run_fedadp(const AdpLaunch& fn, const float* d_x, const void* const* d_src_f
   if (fn.delta != (d_base_f32 == nullptr))
     return set_error(PLATO_AGG_EINVAL, fn.delta ? "this variant takes delta arenas (null baseline)"
                                                 : "delta arenas (null baseline) need a delta variant");
+  // the product entry points never get here with such a pair (adp_for_lr): an explicit tuning variant
+  if (fn.recip && !plato_agg_internal::recip_product_exact(lr))
+    return set_error(PLATO_AGG_EINVAL, "this variant divides by a float64 reciprocal product, which is not the "
+                                       "exact division for lr " + std::to_string(lr) +
+                                           " (an even integer that is no power of two)");
   if ((reinterpret_cast<uintptr_t>(d_x) & 15u) || (reinterpret_cast<uintptr_t>(d_workspace) & 255u))
     return set_error(PLATO_AGG_EINVAL, "x must be 16-byte and the workspace 256-byte aligned");
   if (n_segs == 0 || n_segs >= (1u << 22)) return set_error(PLATO_AGG_EINVAL, "segment count must be in [1, 2^22)");

@@ -472,7 +472,9 @@ __device__ void qsgd_f32_chunk_sp(const QArgs& a, uint32_t c, float (*lut)[kAbs 
 // default's 3.87 VALU instructions per 64 element-clients already keep the SIMDs ~53 % busy beside the
 // LDS array's ~60 % (profiles/r06c_qsgd_pmc.json).  Two levers on it:
 //  * kFastTab: the decode table built with the float64 reciprocal product (RN32(RN64(p) * RN64(1 / d))
-//    = RN32(p / d) for every float pair, tests/test_division.py; fedadp.hip adp_div_lr_f64) instead of the
+//    = RN32(p / d) for every float p when d is not an even integer or is a power of two, common.h
+//    recip_product_exact, tests/test_division.py; at any other d an exact tie between two subnormals
+//    rounds the wrong way, so run_qsgd never launches a kFastTab kernel with one) instead of the
 //    IEEE division's ~10-instruction sequence: the table build was ~a quarter of the VALU instructions;
 //  * kP element groups per lane: each table batch serves kP groups of kG elements (a kP-times longer chunk
 //    per workgroup), so the table build and its two barriers are paid once per kP groups.
@@ -876,9 +878,11 @@ __global__ __launch_bounds__(kBlock) void fedavg_qsgd_kernel(QArgs a) {
 // ---------------------------------------------------------------------------
 // Arithmetic decode (no tables, no LDS, no barriers): x = RN32(p / divisor) as
 // RN32(RN64(p) * RN64(1 / divisor)) with p = RN32(|zeta| * max_v) — the exact float32 division's bits
-// for every float pair (the argument of fedadp.hip adp_div_lr_f64, tests/test_division.py: the float64
-// product lies within 2^-52 of the quotient, which is never that close to a float32 midpoint unless it
-// is one, and then it is a float64 the product rounds to exactly).  The sign is applied afterwards by
+// for every p when the divisor is not an even integer or is a power of two (common.h
+// recip_product_exact, tests/test_division.py: the float64 product lies within 2^-52 of the quotient,
+// which is never that close to a float32 midpoint unless it is one; a quotient on a midpoint between two
+// subnormals exists only for an even integer divisor, and there the product can round the other way, so
+// run_qsgd refuses these variants such a divisor).  The sign is applied afterwards by
 // flipping bit 31 of the decoded value for codes with bit 7 set and |zeta| != 0: round-to-nearest is
 // sign-symmetric, so decode(128 + z) = -decode(z) for z != 0, and code 128 (zeta = -0, the integer 0)
 // decodes as code 0.  A lane owns kG consecutive elements (one kG-byte code load per client), clients in
@@ -1029,6 +1033,11 @@ void launch_qf(const QArgs& a, hipStream_t st, uint32_t nc) {
 struct QVariant {
   int block, u, g;  // threads, clients per table batch, elements per lane
   QFn fn[2];        // [TWO]
+  // recip: the decode is the float64 reciprocal product, exact only for a divisor that
+  // recip_product_exact (common.h) accepts; any other divisor runs `ieee` (the same shape with the IEEE
+  // division) where the variant has one, and is refused (PLATO_AGG_EINVAL) where it has none
+  bool recip = false;
+  QFn ieee[2] = {nullptr, nullptr};
 };
 // The rounds 1-4 sweeps (table-batch widths, two-level batching, resident tables, hybrid arithmetic
 // decode, sign-rotated tables, globally built tables; round 4: software-pipelined lookups, a
@@ -1045,12 +1054,12 @@ const QVariant kQVariants[] = {
     {1024, 8, 8, {&launch_q<1024, 8, false, 8>, &launch_q<1024, 8, true, 8>}},       // 5: round 1 (vector max_v loads)
     {512, 8, 8, {&launch_q<512, 8, false, 8, true>, &launch_q<512, 8, true, 8, true>}},  // 6: the round-4 default
     // round 6: arithmetic decode (float64 reciprocal product, no tables): {block, clients per batch, elements/lane}
-    {256, 4, 8, {&launch_qa<256, 8, 4, false>, &launch_qa<256, 8, 4, true>}},     // 7
-    {256, 8, 8, {&launch_qa<256, 8, 8, false>, &launch_qa<256, 8, 8, true>}},     // 8
-    {256, 4, 16, {&launch_qa<256, 16, 4, false>, &launch_qa<256, 16, 4, true>}},  // 9
-    {128, 4, 16, {&launch_qa<128, 16, 4, false>, &launch_qa<128, 16, 4, true>}},  // 10
-    {64, 4, 16, {&launch_qa<64, 16, 4, false>, &launch_qa<64, 16, 4, true>}},     // 11
-    {256, 2, 16, {&launch_qa<256, 16, 2, false>, &launch_qa<256, 16, 2, true>}},  // 12
+    {256, 4, 8, {&launch_qa<256, 8, 4, false>, &launch_qa<256, 8, 4, true>}, true},     // 7
+    {256, 8, 8, {&launch_qa<256, 8, 8, false>, &launch_qa<256, 8, 8, true>}, true},     // 8
+    {256, 4, 16, {&launch_qa<256, 16, 4, false>, &launch_qa<256, 16, 4, true>}, true},  // 9
+    {128, 4, 16, {&launch_qa<128, 16, 4, false>, &launch_qa<128, 16, 4, true>}, true},  // 10
+    {64, 4, 16, {&launch_qa<64, 16, 4, false>, &launch_qa<64, 16, 4, true>}, true},     // 11
+    {256, 2, 16, {&launch_qa<256, 16, 2, false>, &launch_qa<256, 16, 2, true>}, true},  // 12
     // round 6: |zeta| tables (128 entries) with the sign flipped into bit 31 (kAbs)
     {256, 8, 8, {&launch_q<256, 8, false, 8, true, true>, &launch_q<256, 8, true, 8, true, true>}},      // 13
     {256, 16, 8, {&launch_q<256, 16, false, 8, true, true>, &launch_q<256, 16, true, 8, true, true>}},   // 14
@@ -1065,33 +1074,36 @@ const QVariant kQVariants[] = {
     {512, 8, 8, {&launch_qs<512, 8, false, 8, false>, &launch_qs<512, 8, true, 8, false>}},     // 22
     {128, 8, 8, {&launch_qs<128, 8, false, 8, false>, &launch_qs<128, 8, true, 8, false>}},     // 23
     // round 6: kP element groups per lane per table batch, float64-product table decode ({block, U, G * P})
-    {256, 8, 8, {&launch_qm<256, 8, false, 8, 1, true>, &launch_qm<256, 8, true, 8, 1, true>}},    // 24: P 1, fast tables
-    {256, 8, 16, {&launch_qm<256, 8, false, 8, 2, true>, &launch_qm<256, 8, true, 8, 2, true>}},   // 25: P 2, fast tables
+    {256, 8, 8, {&launch_qm<256, 8, false, 8, 1, true>, &launch_qm<256, 8, true, 8, 1, true>}, true},    // 24: P 1, fast tables
+    {256, 8, 16, {&launch_qm<256, 8, false, 8, 2, true>, &launch_qm<256, 8, true, 8, 2, true>}, true},   // 25: P 2, fast tables
     {256, 8, 16, {&launch_qm<256, 8, false, 8, 2, false>, &launch_qm<256, 8, true, 8, 2, false>}}, // 26: P 2, IEEE tables
-    {128, 8, 16, {&launch_qm<128, 8, false, 8, 2, true>, &launch_qm<128, 8, true, 8, 2, true>}},   // 27: P 2, 128 threads
-    {256, 8, 32, {&launch_qm<256, 8, false, 8, 4, true>, &launch_qm<256, 8, true, 8, 4, true>}},   // 28: P 4
-    {256, 4, 16, {&launch_qm<256, 4, false, 8, 2, true>, &launch_qm<256, 4, true, 8, 2, true>}},   // 29: P 2, U 4 (default)
-    {256, 4, 8, {&launch_qm<256, 4, false, 8, 1, true>, &launch_qm<256, 4, true, 8, 1, true>}},    // 30: P 1, U 4
+    {128, 8, 16, {&launch_qm<128, 8, false, 8, 2, true>, &launch_qm<128, 8, true, 8, 2, true>}, true},   // 27: P 2, 128 threads
+    {256, 8, 32, {&launch_qm<256, 8, false, 8, 4, true>, &launch_qm<256, 8, true, 8, 4, true>}, true},   // 28: P 4
+    {256, 4, 16, {&launch_qm<256, 4, false, 8, 2, true>, &launch_qm<256, 4, true, 8, 2, true>}, true},   // 29: P 2, U 4 (default)
+    {256, 4, 8, {&launch_qm<256, 4, false, 8, 1, true>, &launch_qm<256, 4, true, 8, 1, true>}, true},    // 30: P 1, U 4
     {256, 4, 16, {&launch_qm<256, 4, false, 8, 2, false>, &launch_qm<256, 4, true, 8, 2, false>}}, // 31: P 2, U 4, IEEE
-    {256, 4, 32, {&launch_qm<256, 4, false, 8, 4, true>, &launch_qm<256, 4, true, 8, 4, true>}},   // 32: P 4, U 4
-    {256, 2, 16, {&launch_qm<256, 2, false, 8, 2, true>, &launch_qm<256, 2, true, 8, 2, true>}},   // 33: P 2, U 2
-    {512, 4, 16, {&launch_qm<512, 4, false, 8, 2, true>, &launch_qm<512, 4, true, 8, 2, true>}},   // 34: P 2, U 4, 512
-    {128, 4, 16, {&launch_qm<128, 4, false, 8, 2, true>, &launch_qm<128, 4, true, 8, 2, true>}},   // 35: P 2, U 4, 128
-    {256, 4, 24, {&launch_qm<256, 4, false, 8, 3, true>, &launch_qm<256, 4, true, 8, 3, true>}},   // 36: P 3, U 4
-    {256, 4, 16, {&launch_qm<256, 4, false, 4, 4, true>, &launch_qm<256, 4, true, 4, 4, true>}},   // 37: G 4 x P 4, U 4
+    {256, 4, 32, {&launch_qm<256, 4, false, 8, 4, true>, &launch_qm<256, 4, true, 8, 4, true>}, true},   // 32: P 4, U 4
+    {256, 2, 16, {&launch_qm<256, 2, false, 8, 2, true>, &launch_qm<256, 2, true, 8, 2, true>}, true},   // 33: P 2, U 2
+    {512, 4, 16, {&launch_qm<512, 4, false, 8, 2, true>, &launch_qm<512, 4, true, 8, 2, true>}, true},   // 34: P 2, U 4, 512
+    {128, 4, 16, {&launch_qm<128, 4, false, 8, 2, true>, &launch_qm<128, 4, true, 8, 2, true>}, true},   // 35: P 2, U 4, 128
+    {256, 4, 24, {&launch_qm<256, 4, false, 8, 3, true>, &launch_qm<256, 4, true, 8, 3, true>}, true},   // 36: P 3, U 4
+    {256, 4, 16, {&launch_qm<256, 4, false, 4, 4, true>, &launch_qm<256, 4, true, 4, 4, true>}, true},   // 37: G 4 x P 4, U 4
     // round 6: as 24-37 with the next batch's codes in flight during the current batch ({block, U, G * P})
-    {256, 4, 16, {&launch_qf<256, 4, false, 8, 2, true>, &launch_qf<256, 4, true, 8, 2, true>}},   // 38: P 2, U 4
-    {256, 8, 16, {&launch_qf<256, 8, false, 8, 2, true>, &launch_qf<256, 8, true, 8, 2, true>}},   // 39: P 2, U 8
-    {256, 4, 8, {&launch_qf<256, 4, false, 8, 1, true>, &launch_qf<256, 4, true, 8, 1, true>}},    // 40: P 1, U 4
-    {256, 2, 16, {&launch_qf<256, 2, false, 8, 2, true>, &launch_qf<256, 2, true, 8, 2, true>}},   // 41: P 2, U 2
-    {512, 4, 16, {&launch_qf<512, 4, false, 8, 2, true>, &launch_qf<512, 4, true, 8, 2, true>}},   // 42: P 2, U 4, 512
+    {256, 4, 16, {&launch_qf<256, 4, false, 8, 2, true>, &launch_qf<256, 4, true, 8, 2, true>}, true},   // 38: P 2, U 4
+    {256, 8, 16, {&launch_qf<256, 8, false, 8, 2, true>, &launch_qf<256, 8, true, 8, 2, true>}, true},   // 39: P 2, U 8
+    {256, 4, 8, {&launch_qf<256, 4, false, 8, 1, true>, &launch_qf<256, 4, true, 8, 1, true>}, true},    // 40: P 1, U 4
+    {256, 2, 16, {&launch_qf<256, 2, false, 8, 2, true>, &launch_qf<256, 2, true, 8, 2, true>}, true},   // 41: P 2, U 2
+    {512, 4, 16, {&launch_qf<512, 4, false, 8, 2, true>, &launch_qf<512, 4, true, 8, 2, true>}, true},   // 42: P 2, U 4, 512
 };
 #else  // libplato_agg.so: the default only
 // = tuning variant 29 (round 6): two 8-element groups per lane per table batch of 4 clients, tables by
 // the float64 reciprocal product: 0.290 against 0.308 ms for the round-5 default (tuning variant 0),
-// interleaved on one box (profiles/r06g_qsgd_variants.log)
+// interleaved on one box (profiles/r06g_qsgd_variants.log); a divisor the product is not exact for (an
+// even integer that is no power of two: levels 99, 151, 155, ...) gets the same shape with IEEE tables
+// (tuning variant 31)
 const QVariant kQVariants[] = {
-    {256, 4, 16, {&launch_qm<256, 4, false, 8, 2, true>, &launch_qm<256, 4, true, 8, 2, true>}},  // 0 (default)
+    {256, 4, 16, {&launch_qm<256, 4, false, 8, 2, true>, &launch_qm<256, 4, true, 8, 2, true>}, true,
+     {&launch_qm<256, 4, false, 8, 2, false>, &launch_qm<256, 4, true, 8, 2, false>}},  // 0 (default)
 };
 #endif
 constexpr int kNumQVariants = sizeof(kQVariants) / sizeof(kQVariants[0]);
@@ -1138,7 +1150,17 @@ int run_qsgd(int variant, const uint8_t* const* d_codes_f32, const uint8_t* cons
   a.nci = n_chunks_i64;
   a.divisor = divisor;
   a.K = K;
-  kQVariants[variant].fn[d_s ? 1 : 0](a, stream, uint32_t(nc));
+  const QVariant& qv = kQVariants[variant];
+  QFn fn = qv.fn[d_s ? 1 : 0];
+  if (qv.recip && !plato_agg_internal::recip_product_exact(divisor)) {
+    fn = qv.ieee[d_s ? 1 : 0];
+    if (!fn)
+      return set_error(PLATO_AGG_EINVAL, "qsgd variant " + std::to_string(variant) +
+                                             " decodes by a float64 reciprocal product, which is not the exact "
+                                             "division for divisor " + std::to_string(divisor) +
+                                             " (an even integer that is no power of two)");
+  }
+  fn(a, stream, uint32_t(nc));
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return set_error(PLATO_AGG_EHIP, std::string("fedavg_qsgd launch: ") + hipGetErrorString(err));
   return clear_error();

@@ -172,7 +172,8 @@ def f64_reference(xs: np.ndarray, w) -> np.ndarray:
 DECODE_CAPS = (4, 256, 4096)
 DECODE_KS = (1, 2, 5)
 QSGD_MAX_V = np.array([0.0, 1e-45, 1.17e-38, 1e-3, 1.0, 3.4e38, np.inf, np.nan], dtype=np.float32)
-QSGD_DIVISORS = (1, 3, 127, 255)
+# 98 and 246: even, no power of two, where an exact tie between two subnormals exists (tests/test_division.py)
+QSGD_DIVISORS = (1, 3, 127, 255, 98, 246)
 NATIVE_I64 = np.array([0, 1, -1, 2**24 + 1, -(2**24 + 1), 2**24 + 3, -(2**24 + 3), 2**53 + 1, I64_MIN, I64_MAX],
                       dtype=np.int64)  # 2^24 + 1 and 2^24 + 3 are ties: RNE gives 2^24 and 2^24 + 4
 

@@ -168,11 +168,13 @@ def test_entry_norm_kernels_agree_bitwise(engine, k, deltas):
             assert outs[0][:, e_i].tobytes() == ref.torch_cpu_norm_f32(np.ascontiguousarray(rows)).tobytes(), e.name
 
 
-@pytest.mark.parametrize("k,deltas", [(96, False), (97, False), (129, True), (193, False), (255, True)])
+@pytest.mark.parametrize("k,deltas", [(95, True), (96, False), (97, False), (127, False), (128, True), (129, True),
+                                      (193, False), (255, True)])
 def test_entry_norms_default_from_k96_matches_oracle(engine, k, deltas):
     """The product entry point at K >= 96 (two clients of one entry per workgroup sharing the baseline
-    tiles, four from K = 192, in one chain wave; a ragged K leaves a partial last group) == torch CPU
-    order, both arena tails."""
+    tiles, four from K = 128, in one chain wave; a ragged K leaves a partial last group) == torch CPU
+    order, both arena tails; both sides of each switch (95 / 96: one client to two, 127 / 128: two to
+    four)."""
     from plato_amd import _lib
 
     for spec in (RING_SPEC, RING_SPEC[:-1] + [("z", (12291,), "f32")]):
@@ -767,3 +769,71 @@ def test_fedadp_dots_many_entries_match_oracle(engine, n_entries, deltas):
         assert loc.dtype == np.float32 and loc.size == layout.n_f32 + layout.n_i64
         assert R.sdot(g, loc).tobytes() == np.float32(inner[i]).tobytes(), i
         assert R.sdot(loc, loc).tobytes() == np.float32(l_sq[i]).tobytes(), i
+
+
+# ------------------------------------------------- FedAdp's division by -lr at a subnormal tie
+ADP_TIE_IDX = (30, 530, 1041, 2011, 3930, 4030, 4095)  # coordinates of "b.weight" (flat position 70 + index)
+ADP_TIE_M = ((1, 1, 1, 1, 1, 1, 1), (0, 1, 2, 3, 5, 8, 13), (100, 1, 1000, 7, 40000, 2, 85000))
+
+
+@pytest.mark.parametrize("lr", [98.0, 0.03])
+@pytest.mark.parametrize("align", [None, "fedadp"])
+@pytest.mark.parametrize("deltas", [False, True], ids=["weight_arenas", "delta_arenas"])
+def test_fedadp_dots_at_subnormal_ties(deltas, align, lr):
+    """loc = -(x - b) / lr where the quotient is exactly a tie between two float32 subnormals: the
+    dividends (2 m + 1) * 49 * 2^-149 under lr = 98 (147 * 2^-149 / 98 = 3 * 2^-150, which IEEE division
+    rounds to 2^-148 and a float64 reciprocal product to 2^-149, tests/test_division.py).  They sit in the
+    second entry in name order (the divided one), at flat positions of a boundary group (100), of whole
+    groups, of the ragged last group (4100) and of sdot's scalar tail (4165); the global gradient is 2^100
+    there and 0 elsewhere, so inner[c] = 2^100 * (the sum of client c's few loc values), exact in float32:
+    one decode off by a subnormal changes its bits.  lr = 98 takes the producers with the IEEE division,
+    lr = 0.03 (no |lr| < 2 has such a tie) the float64 product; both equal numpy's float32 division and
+    sdot order, and the flatten + sdot path."""
+    from oracle import fedavg_oracle as FO
+    from oracle import reductions as R
+
+    tiny = 2.0**-149
+    names = ("a.weight", "b.weight")
+    k = 3
+    engine = FedAvgEngine(DEV)
+    engine.layout_align = align
+    engine.delta_arenas = deltas
+    base = OrderedDict([("a.weight", torch.zeros(70)), ("b.weight", torch.zeros(4099))])
+    idx = np.asarray(ADP_TIE_IDX)
+    deltas_h = []
+    for c in range(k):
+        b = np.zeros(4099, np.float32)
+        b[idx] = [np.float32((-1) ** (c * j) * (2 * m + 1) * 49 * tiny) for j, m in enumerate(ADP_TIE_M[c])]
+        deltas_h.append({"a.weight": np.zeros(70, np.float32), "b.weight": b})
+    g_b = np.zeros(4099, np.float32)
+    g_b[idx] = np.float32(-98.0 * 2.0**100)
+    rnd = engine.begin(base, k)
+    rnd.put_baseline(base)
+    for c in range(k):
+        rnd.put_client(c, OrderedDict((n, torch.from_numpy(deltas_h[c][n])) for n in names))  # b = 0: x is the delta
+    lay = rnd.layout
+    gf = np.zeros(lay.row_f32, np.float32)
+    gf[lay["b.weight"].offset:lay["b.weight"].offset + 4099] = g_b
+    grads = (torch.from_numpy(gf).to(DEV), torch.zeros(lay.row_i64, dtype=torch.float32, device=DEV))
+    inner, g_sq, l_sq = rnd.fedadp_dots(grads, range(k), lr)
+    flat = rnd.fedadp_dots_flat(grads, range(k), lr)
+
+    g = FO.fedadp_flatten({"a.weight": np.zeros(70, np.float32), "b.weight": g_b}, lr)
+    assert g.dtype == np.float32 and g.size == 4169
+    locs = [FO.fedadp_flatten(d, lr) for d in deltas_h]
+    if lr == 98.0:
+        assert np.all(g[70 + idx] == np.float32(2.0**100))
+        # client 0 holds 147 * 2^-149 everywhere: the oracle divides to -2^-148, and inner is sensitive to
+        # the other rounding at any one coordinate
+        assert locs[0].dtype == np.float32 and np.all(locs[0][70 + idx] == np.float32(-(2.0**-148)))
+        for p in 70 + idx:
+            other = locs[0].copy()
+            other[p] = np.float32(-(2.0**-149))
+            assert R.sdot(g, other).tobytes() != R.sdot(g, locs[0]).tobytes(), p
+    assert R.sdot(g, g).tobytes() == np.float32(g_sq).tobytes()
+    for c in range(k):
+        assert R.sdot(g, locs[c]).tobytes() == np.float32(inner[c]).tobytes(), (c, inner[c])
+        assert R.sdot(locs[c], locs[c]).tobytes() == np.float32(l_sq[c]).tobytes(), c
+    assert np.asarray(inner).tobytes() == np.asarray(flat[0]).tobytes()
+    assert np.float32(g_sq).tobytes() == np.float32(flat[1]).tobytes()
+    assert np.asarray(l_sq).tobytes() == np.asarray(flat[2]).tobytes()
