@@ -21,39 +21,9 @@
 //    (b - a)^2 have the same bits, so the matrix is symmetric bitwise.
 //  * mean_rows is a streaming kernel in the shape of the FedAvg one: one coordinate per lane, m
 //    coalesced loads through the wave-uniform pointer table, sequential fp32 adds, one IEEE division.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "common.h"
-#include "plato_agg.h"
+#include "rows.h"
 
 namespace {
-
-int fail(int code, const std::string& msg) { return plato_agg_internal::set_error(code, msg); }
-
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const int64_t gi64;
-
-template <class T>
-__device__ __forceinline__ T sld(const T* p, int i) {
-  return ((__attribute__((address_space(4))) const T*)p)[i];
-}
-
-template <bool I64>
-struct Column;
-template <>
-struct Column<false> {
-  typedef float elem;
-  static __device__ __forceinline__ float load(const float* p, uint64_t e) { return ((gfloat*)p)[e]; }
-};
-template <>
-struct Column<true> {
-  typedef int64_t elem;
-  // torch.cat of fp32 and int64 promotes the counters to fp32, round to nearest even
-  static __device__ __forceinline__ float load(const int64_t* p, uint64_t e) { return (float)((gi64*)p)[e]; }
-};
 
 // ------------------------------------------------------------------ pairwise squared distances
 constexpr int kTile = 32;                     // clients per tile side
@@ -71,11 +41,8 @@ static_assert(kChain % 2 == 0 && kChainPanels >= 1, "a chain covers whole panels
 static_assert(kLoads * kThreads == kRows * kPanel, "the panel divides among the threads");
 
 // Coordinates per chunk of a region of n coordinates: a multiple of the chain's 64 * kChain, chosen by n alone.
-uint64_t chunk_len(uint64_t n) {
-  const uint64_t m = (n + kChainCoords * kMaxChunks - 1) / (kChainCoords * kMaxChunks);
-  return kChainCoords * (m ? m : 1);
-}
-uint32_t num_chunks(uint64_t n) { return n ? uint32_t((n + chunk_len(n) - 1) / chunk_len(n)) : 0; }
+uint64_t chunk_len(uint64_t n) { return chunk_len(n, kChainCoords, kMaxChunks); }
+uint32_t num_chunks(uint64_t n) { return num_chunks(n, kChainCoords, kMaxChunks); }
 uint32_t num_tiles(int K) {
   const uint32_t t = uint32_t(K + kTile - 1) / kTile;
   return t * (t + 1) / 2;
@@ -259,10 +226,6 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(const typename Column<I6
   out[e] = __fdiv_rn(acc, (float)m);
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-constexpr uint64_t kMaxCoords = 1ull << 38;  // per region: 2^30 workgroups of 256 in mean_rows
-
 }  // namespace
 
 extern "C" {
@@ -276,16 +239,15 @@ size_t plato_agg_pairwise_sqdist_workspace(int K, size_t n_f32, size_t n_i64) {
 
 int plato_agg_pairwise_sqdist(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K, size_t n_f32,
                               size_t n_i64, void* d_workspace, double* d_out, hipStream_t stream) {
-  if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "K must be in 1..256");
-  if (n_f32 && !d_x_f32) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
-  if (n_i64 && !d_x_i64) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
-  if (!d_out || !d_workspace) return fail(PLATO_AGG_EINVAL, "null output or workspace pointer");
-  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
-    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
-  if (!aligned(d_out, 16)) return fail(PLATO_AGG_EINVAL, "the distance matrix must be 16-byte aligned");
-  if (!aligned(d_workspace, 256)) return fail(PLATO_AGG_EINVAL, "workspace must be 256-byte aligned");
-  if (n_f32 >= kMaxCoords || n_i64 >= kMaxCoords)
-    return fail(PLATO_AGG_EINVAL, "more than 2^38 coordinates in one call");
+  const char* why = first_refusal({
+      bad_rows(K, "K must be in 1..256"),
+      null_region(n_f32, d_x_f32, d_x_f32, n_i64, d_x_i64, d_x_i64),
+      null_f64_out(d_out, d_workspace),
+      bad_tables(n_f32, d_x_f32, n_i64, d_x_i64),
+      bad_f64_out(d_out, "the distance matrix must be 16-byte aligned", d_workspace),
+      too_many_coords(n_f32, n_i64),
+  });
+  if (why) return fail(PLATO_AGG_EINVAL, why);
   const uint32_t ntiles = num_tiles(K), cf = num_chunks(n_f32), ci = num_chunks(n_i64);
   double* ws = static_cast<double*>(d_workspace);
   if (cf)
@@ -303,15 +265,14 @@ int plato_agg_pairwise_sqdist(const float* const* d_x_f32, const int64_t* const*
 
 int plato_agg_mean_rows(const float* const* d_x_f32, const int64_t* const* d_x_i64, int m, float* d_out_f32,
                         float* d_out_i64_as_f32, size_t n_f32, size_t n_i64, hipStream_t stream) {
-  if (m < 1 || m > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "m must be in 1..256");
-  if (n_f32 && (!d_x_f32 || !d_out_f32)) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
-  if (n_i64 && (!d_x_i64 || !d_out_i64_as_f32)) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
-  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
-    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
-  if ((n_f32 && !aligned(d_out_f32, 16)) || (n_i64 && !aligned(d_out_i64_as_f32, 4)))
-    return fail(PLATO_AGG_EINVAL, "fp32 output must be 16-byte aligned (int64-as-fp32 output: 4)");
-  if (n_f32 >= kMaxCoords || n_i64 >= kMaxCoords)
-    return fail(PLATO_AGG_EINVAL, "more than 2^38 coordinates in one call");
+  const char* why = first_refusal({
+      bad_rows(m, "m must be in 1..256"),
+      null_region(n_f32, d_x_f32, d_out_f32, n_i64, d_x_i64, d_out_i64_as_f32),
+      bad_tables(n_f32, d_x_f32, n_i64, d_x_i64),
+      bad_outputs(n_f32, d_out_f32, n_i64, d_out_i64_as_f32),
+      too_many_coords(n_f32, n_i64),
+  });
+  if (why) return fail(PLATO_AGG_EINVAL, why);
   if (n_f32)
     hipLaunchKernelGGL((mean_rows_kernel<false>), dim3(uint32_t((n_f32 + 255) / 256)), dim3(256), 0, stream, d_x_f32,
                        m, d_out_f32, uint64_t(n_f32));

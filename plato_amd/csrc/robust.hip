@@ -16,48 +16,14 @@
 //    have a 0 in the current bit.  Every loop is a run-time loop over K, so one kernel serves every
 //    K in 1..256 with a few dozen VGPRs and no scratch.  A lane reads only what it wrote itself: no
 //    barrier is needed.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "common.h"
-#include "plato_agg.h"
+#include "rows.h"
 
 namespace {
-
-int fail(int code, const std::string& msg) { return plato_agg_internal::set_error(code, msg); }
-
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const int64_t gi64;
-
-template <class T>
-__device__ __forceinline__ T sld(const T* p, int i) {
-  return ((__attribute__((address_space(4))) const T*)p)[i];
-}
 
 // Order-preserving key of an fp32 bit pattern: unsigned ascending = the total order -nan < -inf < ...
 // < -0 < +0 < ... < +inf < +nan.
 __device__ __forceinline__ uint32_t to_key(uint32_t u) { return u ^ (uint32_t((int32_t)u >> 31) | 0x80000000u); }
 __device__ __forceinline__ uint32_t from_key(uint32_t k) { return k ^ (uint32_t((int32_t)~k >> 31) | 0x80000000u); }
-
-template <bool I64>
-struct Column;
-template <>
-struct Column<false> {
-  typedef float elem;
-  static __device__ __forceinline__ uint32_t bits(const float* p, uint64_t e) {
-    return __float_as_uint(__builtin_nontemporal_load((gfloat*)p + e));
-  }
-};
-template <>
-struct Column<true> {
-  typedef int64_t elem;
-  // torch.cat of fp32 and int64 promotes the counters to fp32, round to nearest even
-  static __device__ __forceinline__ uint32_t bits(const int64_t* p, uint64_t e) {
-    return __float_as_uint((float)__builtin_nontemporal_load((gi64*)p + e));
-  }
-};
 
 constexpr int kWave = 64;  // one-wave workgroups: lane l owns coordinate blockIdx.x * 64 + l
 
@@ -168,8 +134,6 @@ void launch_nearest_mean(const void* x, int K, int trim, float* out, size_t n, h
                      out, uint64_t(n));
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -177,19 +141,18 @@ extern "C" {
 int plato_agg_robust_columns(int mode, const float* const* d_x_f32, const int64_t* const* d_x_i64, int K, int trim,
                              float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32, size_t n_i64,
                              hipStream_t stream) {
-  if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "K must be in 1..256");
-  if (mode != PLATO_AGG_ROBUST_MEDIAN && mode != PLATO_AGG_ROBUST_NEAREST_MEAN)
-    return fail(PLATO_AGG_EINVAL, "unknown robust aggregation mode");
-  if (trim < 0 || 2 * trim >= K) return fail(PLATO_AGG_EINVAL, "trim must satisfy 0 <= 2*trim < K");
-  if (n_f32 && (!d_x_f32 || !d_out_f32)) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
-  if (n_i64 && (!d_x_i64 || !d_out_i64_as_f32)) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
-  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
-    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
-  if ((n_f32 && !aligned(d_out_f32, 16)) || (n_i64 && !aligned(d_out_i64_as_f32, 4)))
-    return fail(PLATO_AGG_EINVAL, "fp32 output must be 16-byte aligned (int64-as-fp32 output: 4)");
-  // one coordinate per lane, at least 64 lanes per workgroup, at most 2^31 - 1 workgroups
-  if (n_f32 / 64 >= 0x7fffffffull || n_i64 / 64 >= 0x7fffffffull)
-    return fail(PLATO_AGG_EINVAL, "more than 2^37 coordinates in one call");
+  const char* why = first_refusal({
+      bad_rows(K, "K must be in 1..256"),
+      mode != PLATO_AGG_ROBUST_MEDIAN && mode != PLATO_AGG_ROBUST_NEAREST_MEAN ? "unknown robust aggregation mode"
+                                                                               : nullptr,
+      trim < 0 || 2 * trim >= K ? "trim must satisfy 0 <= 2*trim < K" : nullptr,
+      null_region(n_f32, d_x_f32, d_out_f32, n_i64, d_x_i64, d_out_i64_as_f32),
+      bad_tables(n_f32, d_x_f32, n_i64, d_x_i64),
+      bad_outputs(n_f32, d_out_f32, n_i64, d_out_i64_as_f32),
+      // one coordinate per lane, at least 64 lanes per workgroup, at most 2^31 - 1 workgroups
+      n_f32 / 64 >= 0x7fffffffull || n_i64 / 64 >= 0x7fffffffull ? "more than 2^37 coordinates in one call" : nullptr,
+  });
+  if (why) return fail(PLATO_AGG_EINVAL, why);
   if (mode == PLATO_AGG_ROBUST_MEDIAN) {
     if (n_f32) launch_median<false>(d_x_f32, K, d_out_f32, n_f32, stream);
     if (n_i64) launch_median<true>(d_x_i64, K, d_out_i64_as_f32, n_i64, stream);

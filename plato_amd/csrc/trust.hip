@@ -18,39 +18,9 @@
 //  * scaled_sum is a streaming kernel in the shape of mean_rows: one coordinate per lane, K coalesced
 //    loads, per row one fp32 multiply, one IEEE division, one multiply and one add, each separately
 //    rounded (the build has -ffp-contract=off).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "common.h"
-#include "plato_agg.h"
+#include "rows.h"
 
 namespace {
-
-int fail(int code, const std::string& msg) { return plato_agg_internal::set_error(code, msg); }
-
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const int64_t gi64;
-
-template <class T>
-__device__ __forceinline__ T sld(const T* p, int i) {
-  return ((__attribute__((address_space(4))) const T*)p)[i];
-}
-
-template <bool I64>
-struct Column;
-template <>
-struct Column<false> {
-  typedef float elem;
-  static __device__ __forceinline__ float load(const float* p, uint64_t e) { return ((gfloat*)p)[e]; }
-};
-template <>
-struct Column<true> {
-  typedef int64_t elem;
-  // torch.cat of fp32 and int64 promotes the counters to fp32, round to nearest even
-  static __device__ __forceinline__ float load(const int64_t* p, uint64_t e) { return (float)((gi64*)p)[e]; }
-};
 
 // ------------------------------------------------------------------ per-client dots and norms
 constexpr int kThreads = 256;
@@ -63,11 +33,8 @@ constexpr uint32_t kMaxChunks = 1024;                 // coordinate chunks per r
 static_assert(kTile % kPass == 0, "a tile is a whole number of passes");
 
 // Coordinates per chunk of a region of n coordinates: a multiple of kTile, chosen by n alone.
-uint64_t chunk_len(uint64_t n) {
-  const uint64_t m = (n + kTile * kMaxChunks - 1) / (kTile * kMaxChunks);
-  return kTile * (m ? m : 1);
-}
-uint32_t num_chunks(uint64_t n) { return n ? uint32_t((n + chunk_len(n) - 1) / chunk_len(n)) : 0; }
+uint64_t chunk_len(uint64_t n) { return chunk_len(n, kTile, kMaxChunks); }
+uint32_t num_chunks(uint64_t n) { return num_chunks(n, kTile, kMaxChunks); }
 uint32_t num_batches(int K) { return uint32_t(K + kU - 1) / kU; }
 
 __device__ __forceinline__ double wave_sum(double x) {
@@ -204,10 +171,6 @@ __global__ __launch_bounds__(256) void scaled_sum_kernel(const typename Column<I
   out[e] = acc;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-constexpr uint64_t kMaxCoords = 1ull << 38;  // per region, as in mean_rows
-
 }  // namespace
 
 extern "C" {
@@ -222,18 +185,18 @@ size_t plato_agg_trust_stats_workspace(int K, size_t n_f32, size_t n_i64) {
 int plato_agg_trust_stats(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K, const float* d_ref_f32,
                           const float* d_ref_i64_as_f32, float eps, size_t n_f32, size_t n_i64, void* d_workspace,
                           double* d_out, hipStream_t stream) {
-  if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "K must be in 1..256");
-  if (n_f32 && (!d_x_f32 || !d_ref_f32)) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
-  if (n_i64 && (!d_x_i64 || !d_ref_i64_as_f32)) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
-  if (!d_out || !d_workspace) return fail(PLATO_AGG_EINVAL, "null output or workspace pointer");
-  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
-    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
-  if ((n_f32 && !aligned(d_ref_f32, 4)) || (n_i64 && !aligned(d_ref_i64_as_f32, 4)))
-    return fail(PLATO_AGG_EINVAL, "the reference vector must be 4-byte aligned");
-  if (!aligned(d_out, 16)) return fail(PLATO_AGG_EINVAL, "the statistics must be 16-byte aligned");
-  if (!aligned(d_workspace, 256)) return fail(PLATO_AGG_EINVAL, "workspace must be 256-byte aligned");
-  if (n_f32 >= kMaxCoords || n_i64 >= kMaxCoords)
-    return fail(PLATO_AGG_EINVAL, "more than 2^38 coordinates in one call");
+  const char* why = first_refusal({
+      bad_rows(K, "K must be in 1..256"),
+      null_region(n_f32, d_x_f32, d_ref_f32, n_i64, d_x_i64, d_ref_i64_as_f32),
+      null_f64_out(d_out, d_workspace),
+      bad_tables(n_f32, d_x_f32, n_i64, d_x_i64),
+      (n_f32 && !aligned(d_ref_f32, 4)) || (n_i64 && !aligned(d_ref_i64_as_f32, 4))
+          ? "the reference vector must be 4-byte aligned"
+          : nullptr,
+      bad_f64_out(d_out, "the statistics must be 16-byte aligned", d_workspace),
+      too_many_coords(n_f32, n_i64),
+  });
+  if (why) return fail(PLATO_AGG_EINVAL, why);
   if (!n_f32 && !n_i64) return plato_agg_internal::clear_error();
   const uint32_t cf = num_chunks(n_f32), ci = num_chunks(n_i64), nb = num_batches(K) + 1;
   const uint32_t nrows = 3 * uint32_t(K) + 1;
@@ -253,17 +216,16 @@ int plato_agg_trust_stats(const float* const* d_x_f32, const int64_t* const* d_x
 int plato_agg_scaled_sum(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K, const float* d_mul,
                          const float* d_div, float post, float* d_out_f32, float* d_out_i64_as_f32, size_t n_f32,
                          size_t n_i64, hipStream_t stream) {
-  if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K) return fail(PLATO_AGG_EINVAL, "K must be in 1..256");
-  if (n_f32 && (!d_x_f32 || !d_out_f32)) return fail(PLATO_AGG_EINVAL, "null fp32 arena pointer");
-  if (n_i64 && (!d_x_i64 || !d_out_i64_as_f32)) return fail(PLATO_AGG_EINVAL, "null int64 arena pointer");
-  if (!d_mul || !d_div) return fail(PLATO_AGG_EINVAL, "null scalar table pointer");
-  if ((n_f32 && !aligned(d_x_f32, 8)) || (n_i64 && !aligned(d_x_i64, 8)))
-    return fail(PLATO_AGG_EINVAL, "pointer tables must be 8-byte aligned");
-  if (!aligned(d_mul, 4) || !aligned(d_div, 4)) return fail(PLATO_AGG_EINVAL, "scalar tables must be 4-byte aligned");
-  if ((n_f32 && !aligned(d_out_f32, 16)) || (n_i64 && !aligned(d_out_i64_as_f32, 4)))
-    return fail(PLATO_AGG_EINVAL, "fp32 output must be 16-byte aligned (int64-as-fp32 output: 4)");
-  if (n_f32 >= kMaxCoords || n_i64 >= kMaxCoords)
-    return fail(PLATO_AGG_EINVAL, "more than 2^38 coordinates in one call");
+  const char* why = first_refusal({
+      bad_rows(K, "K must be in 1..256"),
+      null_region(n_f32, d_x_f32, d_out_f32, n_i64, d_x_i64, d_out_i64_as_f32),
+      !d_mul || !d_div ? "null scalar table pointer" : nullptr,
+      bad_tables(n_f32, d_x_f32, n_i64, d_x_i64),
+      !aligned(d_mul, 4) || !aligned(d_div, 4) ? "scalar tables must be 4-byte aligned" : nullptr,
+      bad_outputs(n_f32, d_out_f32, n_i64, d_out_i64_as_f32),
+      too_many_coords(n_f32, n_i64),
+  });
+  if (why) return fail(PLATO_AGG_EINVAL, why);
   if (n_f32)
     hipLaunchKernelGGL((scaled_sum_kernel<false>), dim3(uint32_t((n_f32 + 255) / 256)), dim3(256), 0, stream, d_x_f32,
                        K, d_mul, d_div, post, d_out_f32, uint64_t(n_f32));

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, same_f32_bits
+from .robust import RobustAggregates, RobustLaunches
 from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key, payload_fingerprint
 
 
@@ -154,8 +155,9 @@ class _Stager:
         stream.wait_stream(self.stream)
 
 
-class FedAvgEngine:
-    """HIP FedAvg aggregation on one GPU (one process per GPU)."""
+class FedAvgEngine(RobustAggregates):
+    """HIP FedAvg aggregation on one GPU (one process per GPU); the detector example's robust
+    aggregators are ``plato_amd.robust``'s."""
 
     #: QSGD kernel variant (tuning / tests; None = the library default)
     qsgd_variant: int | None = None
@@ -475,88 +477,6 @@ class FedAvgEngine:
         rnd.launch(weights, scales)
         return rnd.result()
 
-    def aggregate_robust(self, payloads: Sequence[Mapping[str, torch.Tensor]], mode: str = "median",
-                         trim: int = 0) -> "OrderedDict[str, torch.Tensor]":
-        """The detector example's order-statistic aggregators over K native payloads, on the GPU.
-
-        ``mode="median"``: the coordinate-wise lower median (``aggregations.median``).
-        ``mode="nearest_mean"``: the mean of the ``K - 2 * trim`` values nearest that median
-        (``aggregations.trimmed_mean``, whose own ``num_attackers`` is 0).  Returns CPU float32 tensors
-        for every entry, the int64 counters included, as the reference does.
-        """
-        k = len(payloads)
-        if k == 0:
-            raise ValueError("no client payloads to aggregate")
-        if k > _lib.PLATO_AGG_ROBUST_MAX_K:
-            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, got {k}")
-        codec = payload_codec(payloads[0])
-        if codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
-        rnd = self.begin(payloads[0], k)
-        rnd.deltas = False  # no baseline: the rows stay weights
-        for i, sd in enumerate(payloads):
-            if not rnd.adopt(i, sd):
-                rnd.put_client(i, sd)
-        rnd.launch_robust(mode, trim)
-        return rnd.result()
-
-    def aggregate_multi_krum(self, payloads: Sequence[Mapping[str, torch.Tensor]], f: int = 2
-                             ) -> "OrderedDict[str, torch.Tensor]":
-        """The detector example's ``Multi-krum`` (``aggregations.multi_krum``) over K native payloads, on
-        the GPU: the mean of the ``K - 2f - 2`` clients its distance scores select.  Returns CPU float32
-        tensors for every entry, the int64 counters included, as the reference does."""
-        if 0 < len(payloads) <= 2 * int(f) + 2:
-            raise ValueError(f"Multi-Krum with f = {int(f)} needs more than {2 * int(f) + 2} clients, "
-                             f"got {len(payloads)}")
-        rnd = self._stage_selected(payloads)
-        rnd.launch_multi_krum(f)
-        self.last_selected = rnd.selected
-        return rnd.result()
-
-    def aggregate_bulyan(self, payloads: Sequence[Mapping[str, torch.Tensor]], f: int
-                         ) -> "OrderedDict[str, torch.Tensor]":
-        """The detector example's ``Bulyan`` (``aggregations.bulyan``) over K native payloads, on the GPU:
-        its distance scores select theta = min(K - 2f, K - 2 - f) clients, and every coordinate is the
-        mean of the theta - 2f selected values nearest their median.  K, the reference's
-        ``clients.total_clients``, is the number of payloads.  Returns CPU float32 tensors for every
-        entry, the int64 counters included, as the reference does."""
-        from .krum import bulyan_min_clients
-
-        if payloads and (int(f) < 0 or len(payloads) < bulyan_min_clients(f)):
-            raise ValueError(f"Bulyan with f = {int(f)} needs at least {bulyan_min_clients(max(int(f), 0))} clients, "
-                             f"got {len(payloads)}")
-        rnd = self._stage_selected(payloads)
-        rnd.launch_bulyan(f)
-        self.last_selected = rnd.selected
-        return rnd.result()
-
-    def aggregate_fltrust(self, payloads: Sequence[Mapping[str, torch.Tensor]]
-                          ) -> "OrderedDict[str, torch.Tensor]":
-        """The detector example's ``Fl-trust`` (``aggregations.fl_trust``) over K native payloads, on the
-        GPU: every client weighed by its clipped cosine with the mean model and rescaled to the mean's
-        norm.  ``self.last_trust`` holds the scalars (``plato_amd.trust.fltrust_weights``).  Returns CPU
-        float32 tensors for every entry, the int64 counters included, as the reference does."""
-        rnd = self._stage_selected(payloads)
-        rnd.launch_fltrust()
-        return rnd.result()
-
-    def _stage_selected(self, payloads: Sequence[Mapping[str, torch.Tensor]]) -> "AggregationRound":
-        """A round with K native payloads staged as weights, for the distance-based aggregators."""
-        k = len(payloads)
-        if k == 0:
-            raise ValueError("no client payloads to aggregate")
-        if k > _lib.PLATO_AGG_ROBUST_MAX_K:
-            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, got {k}")
-        codec = payload_codec(payloads[0])
-        if codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
-        rnd = self.begin(payloads[0], k)
-        rnd.deltas = False  # no baseline: the rows stay weights
-        for i, sd in enumerate(payloads):
-            if not rnd.adopt(i, sd):
-                rnd.put_client(i, sd)
-        return rnd
-
     def aggregate_deltas(self, deltas_received: Sequence[Mapping[str, torch.Tensor]],
                          weights: Sequence[float], scales: Sequence[float] | None = None
                          ) -> "OrderedDict[str, torch.Tensor]":
@@ -699,8 +619,9 @@ class _KernelTimer:
         return False
 
 
-class AggregationRound:
-    """One aggregation: client rows staged H2D (in any order), then one launch.
+class AggregationRound(RobustLaunches):
+    """One aggregation: client rows staged H2D (in any order), then one launch (``launch_robust`` and the
+    other robust launches: ``plato_amd.robust``).
 
     Rows are slots; the summation order is given at :meth:`launch` time by
     ``order`` (default: slot order), matching ``self.updates`` order in the
@@ -961,210 +882,6 @@ class AggregationRound:
         e1.record(stream)
         self._kernel_events = (e0, e1)
         self._fetch(stream, out_f, out_i, (tf, ti, w64, wi))
-
-    def launch_robust(self, mode: str = "median", trim: int = 0, order: Sequence[int] | None = None) -> None:
-        """Coordinate-wise robust aggregation of the staged client rows (``plato_agg_robust_columns``).
-
-        ``mode="median"`` is ``aggregations.median`` of the reference's detector example
-        (examples/detector/aggregations.py): ``torch.median(dim=0)`` of the flattened models, the
-        lower median per coordinate.  ``mode="nearest_mean"`` is ``aggregations.trimmed_mean``: per
-        coordinate the mean of the ``K - 2 * trim`` values nearest that median, equally distant ones
-        taken in table order (``0 <= 2 * trim < K``; the reference's own ``num_attackers`` is 0).  No
-        baseline is read.  Every entry of the result is float32, the int64 counters included
-        (``flatten_weights`` promotes them).
-        """
-        if mode not in _lib.PLATO_AGG_ROBUST:
-            raise ValueError(f"unknown robust aggregation mode {mode!r} (supported: {sorted(_lib.PLATO_AGG_ROBUST)})")
-        if self.codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads; this round holds {self.codec} codes")
-        self._raw_only("launch_robust")
-        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else list(order)
-        slots = self._check_slots(order)
-        eng, lay = self.engine, self.layout
-        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
-        self._k = len(slots)
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        n_i = lay.n_i64
-        with self._timed("robust_" + mode, stream):
-            _lib.call("plato_agg_robust_columns", _lib.PLATO_AGG_ROBUST[mode], _ptr(tf), _ptr(ti) if n_i else None,
-                      len(slots), int(trim), _ptr(out_f), _ptr(out_i) if n_i else None, lay.n_f32, n_i,
-                      _stream_handle(stream))
-        e1.record(stream)
-        self._kernel_events = (e0, e1)
-        self._robust = True
-        self._fetch(stream, out_f, out_i, (tf, ti))
-
-    def _distance_rows(self, what: str, order: Sequence[int] | None):
-        """(slots, fp32 pointer table, int64 pointer table, stream) of a distance-based launch, the
-        stream ordered behind the staged copies.  The refusals of :meth:`launch_robust`."""
-        if self.codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads; this round holds {self.codec} codes")
-        self._raw_only(what)
-        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else list(order)
-        slots = self._check_slots(order)
-        if len(slots) > _lib.PLATO_AGG_ROBUST_MAX_K:
-            raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, "
-                             f"got {len(slots)}")
-        if not self.layout.packed:
-            raise ValueError(f"{what} sums over the whole fp32 region: the arena must have no alignment padding")
-        eng = self.engine
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        return slots, tf, ti, stream
-
-    def _pairwise_sqdist(self, k: int, tf, ti, stream) -> np.ndarray:
-        eng, lay = self.engine, self.layout
-        n_i = lay.n_i64
-        nbytes = _lib.lib().plato_agg_pairwise_sqdist_workspace(k, lay.n_f32, n_i)
-        work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=eng.device)
-        out = torch.empty((k, k), dtype=torch.float64, device=eng.device)
-        with self._timed("pairwise_sqdist", stream):
-            _lib.call("plato_agg_pairwise_sqdist", _ptr(tf), _ptr(ti) if n_i else None, k, lay.n_f32, n_i,
-                      _ptr(work), _ptr(out), _stream_handle(stream))
-        dist = out.cpu().numpy()  # stream-ordered, blocking: the selection runs on the host
-        del work
-        return dist
-
-    def launch_pairwise_sqdist(self, order: Sequence[int] | None = None) -> np.ndarray:
-        """The [K, K] float64 matrix of squared L2 distances between the staged client rows, over the
-        whole flattened model (``plato_agg_pairwise_sqdist``): entry [i, j] is
-        ``torch.norm(x_order[i] - x_order[j]) ** 2`` of the reference's distance-based aggregators and
-        detectors (examples/detector/aggregations.py:185-192), with fp32 differences and a float64
-        sum.  Synchronises: the matrix is returned on the host."""
-        slots, tf, ti, stream = self._distance_rows("launch_pairwise_sqdist", order)
-        dist = self._pairwise_sqdist(len(slots), tf, ti, stream)
-        self._resolve_timers()
-        return dist
-
-    def launch_multi_krum(self, f: int = 2, order: Sequence[int] | None = None) -> None:
-        """``aggregations.multi_krum`` of the reference's detector example over the staged client rows:
-        the distance matrix on the device, the selection on the host (``plato_amd.krum``), then the mean
-        of the selected rows in selection order (``plato_agg_mean_rows``).  ``self.selected`` holds the
-        selected client slots in selection order.  No baseline is read; every entry of the result is
-        float32, the int64 counters included."""
-        from .krum import multi_krum_select
-
-        f = int(f)
-
-        def check(k):
-            if k <= 2 * f + 2:
-                raise ValueError(f"Multi-Krum with f = {f} needs more than {2 * f + 2} clients, got {k}")
-
-        def mean(sf, si, m, out_f, out_i, stream):
-            lay = self.layout
-            with self._timed("mean_rows", stream):
-                _lib.call("plato_agg_mean_rows", _ptr(sf), _ptr(si) if lay.n_i64 else None, m, _ptr(out_f),
-                          _ptr(out_i) if lay.n_i64 else None, lay.n_f32, lay.n_i64, _stream_handle(stream))
-
-        self._launch_selected("launch_multi_krum", order, check, lambda dist: multi_krum_select(dist, f), mean)
-
-    def launch_bulyan(self, f: int, order: Sequence[int] | None = None) -> None:
-        """``aggregations.bulyan`` of the reference's detector example over the staged client rows: the
-        distance matrix on the device, the selection of theta = min(K - 2f, K - 2 - f) clients on the
-        host (``plato_amd.krum.bulyan_select``), then per coordinate the mean of the theta - 2f selected
-        values nearest their median (``plato_agg_robust_columns``, nearest-mean mode, over the selected
-        rows in selection order).  ``self.selected`` holds the selected client slots in selection order.
-        No baseline is read; every entry of the result is float32, the int64 counters included."""
-        from .krum import bulyan_min_clients, bulyan_select
-
-        f = int(f)
-
-        def check(k):
-            if f < 0 or k < bulyan_min_clients(f):
-                raise ValueError(f"Bulyan with f = {f} needs at least {bulyan_min_clients(max(f, 0))} clients, got {k}")
-
-        def nearest_mean(sf, si, m, out_f, out_i, stream):
-            lay = self.layout
-            with self._timed("robust_nearest_mean", stream):
-                _lib.call("plato_agg_robust_columns", _lib.PLATO_AGG_ROBUST["nearest_mean"], _ptr(sf),
-                          _ptr(si) if lay.n_i64 else None, m, f, _ptr(out_f), _ptr(out_i) if lay.n_i64 else None,
-                          lay.n_f32, lay.n_i64, _stream_handle(stream))
-
-        self._launch_selected("launch_bulyan", order, check, lambda dist: bulyan_select(dist, f), nearest_mean)
-
-    def launch_fltrust(self, order: Sequence[int] | None = None) -> None:
-        """``aggregations.fl_trust`` of the reference's detector example over the staged client rows: the
-        sequential mean of the rows (``plato_agg_mean_rows``), every client's dot with it and the norms
-        in one pass (``plato_agg_trust_stats``), the cosines, their clip and normalisation on the host
-        (``plato_amd.trust.fltrust_weights``, after a blocking read of the ``3K + 1`` sums), then the sum
-        of the rows scaled by ``w_k / |x_k + 1e-9| * |mean|`` in table order (``plato_agg_scaled_sum``).
-        ``self.trust`` holds the scalars.  No baseline is read; every entry of the result is float32,
-        the int64 counters included."""
-        from .trust import EPS, fltrust_weights
-
-        slots, tf, ti, stream = self._distance_rows("launch_fltrust", order)
-        eng, lay = self.engine, self.layout
-        k, n_i = len(slots), lay.n_i64
-        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
-        self._k = 3 * k  # algorithmic_bytes: the rows are read by the mean, the statistics and the sum
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        mean_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        mean_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        with self._timed("mean_rows", stream):
-            _lib.call("plato_agg_mean_rows", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(mean_f),
-                      _ptr(mean_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
-        nbytes = _lib.lib().plato_agg_trust_stats_workspace(k, lay.n_f32, n_i)
-        work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=eng.device)
-        stats = torch.empty(3 * k + 1, dtype=torch.float64, device=eng.device)
-        with self._timed("trust_stats", stream):
-            _lib.call("plato_agg_trust_stats", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(mean_f),
-                      _ptr(mean_i) if n_i else None, EPS, lay.n_f32, n_i, _ptr(work), _ptr(stats),
-                      _stream_handle(stream))
-        host_stats = stats.cpu().numpy()  # stream-ordered, blocking: the scalars are formed on the host
-        t0 = time.perf_counter()
-        self.trust = eng.last_trust = fltrust_weights(host_stats, k, EPS)
-        self.timings["trust_scalars_ms"] = (time.perf_counter() - t0) * 1e3
-        scal = torch.from_numpy(np.concatenate([self.trust["weights"], self.trust["div"]])).to(eng.device)
-        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        with self._timed("trust_combine", stream):
-            _lib.call("plato_agg_scaled_sum", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(scal),
-                      scal.data_ptr() + 4 * k, float(self.trust["nm"]), _ptr(out_f), _ptr(out_i) if n_i else None,
-                      lay.n_f32, n_i, _stream_handle(stream))
-        e1.record(stream)
-        self._kernel_events = (e0, e1)
-        self._robust = True
-        self._fetch(stream, out_f, out_i, (tf, ti, mean_f, mean_i, work, stats, scal))
-
-    def _launch_selected(self, what: str, order, check, select, combine) -> None:
-        """The distance-based aggregators' common path: ``check(K)`` refuses a K too small, the distance
-        matrix is computed on the device, ``select(dist)`` picks rows on the host, and
-        ``combine(sf, si, m, out_f, out_i, stream)`` launches the kernel that turns the pointer tables of
-        the m selected rows, in selection order, into the result."""
-        slots, tf, ti, stream = self._distance_rows(what, order)
-        check(len(slots))
-        eng, lay = self.engine, self.layout
-        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
-        self._k = len(slots)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        dist = self._pairwise_sqdist(len(slots), tf, ti, stream)
-        t0 = time.perf_counter()
-        picks = select(dist)
-        self.timings["select_ms"] = (time.perf_counter() - t0) * 1e3
-        self.selected = eng.last_selected = [slots[p] for p in picks]
-        self._k = len(slots) + len(picks)  # algorithmic_bytes: K rows for the distances, then the selected ones again
-        sf, si = eng._pointer_tables(np.asarray([self._pf[i] for i in self.selected], dtype=np.int64),
-                                     np.asarray([self._pi[i] for i in self.selected], dtype=np.int64))
-        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        combine(sf, si, len(picks), out_f, out_i, stream)
-        e1.record(stream)
-        self._kernel_events = (e0, e1)
-        self._robust = True
-        self._fetch(stream, out_f, out_i, (tf, ti, sf, si))
 
     def _fetch(self, stream, out_f: torch.Tensor, out_i: torch.Tensor, keep=()) -> None:
         """D2H into pooled pinned buffers, stream-ordered; result() only waits."""

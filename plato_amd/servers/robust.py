@@ -8,12 +8,12 @@ others and averages the selected ones: distances and mean on the GPU (``plato_ag
 ``plato_agg_mean_rows``), the selection on the host (``plato_amd.krum``).  Its ``Trimmed-mean`` and
 ``Bulyan`` end in the mean of the values nearest the coordinate-wise median (the nearest-mean mode of
 ``plato_agg_robust_columns``), ``Bulyan`` after a selection of Multi-krum's kind; they are
-:class:`DetectorAggregationMixin`'s, which hands every other name to its parent.  Its ``Fl-trust`` weighs
+:class:`DetectorAggregationMixin`'s, which adds them to its parent's names.  Its ``Fl-trust`` weighs
 every client by its clipped cosine with the mean model (``plato_agg_mean_rows``,
 ``plato_agg_trust_stats``, the scalars on the host in ``plato_amd.trust``, ``plato_agg_scaled_sum``); it is
-:class:`TrustAggregationMixin`'s, which again hands every other name to its parent.  The detector server's
-``weights_received`` pipeline (attack simulation, filters) is the base class's and runs before this
-hook, unchanged::
+:class:`TrustAggregationMixin`'s, which again adds it to its parent's.  One ``aggregate_weights`` serves
+the three: a class differs in its table of names only.  The detector server's ``weights_received``
+pipeline (attack simulation, filters) is the base class's and runs before this hook, unchanged::
 
     Server = make_server(base=detector_server.Server, mixin=RobustAggregationMixin)
 """
@@ -23,12 +23,6 @@ from __future__ import annotations
 from .. import tracing
 from ..arena import payload_codec
 from .fedavg import FusedAggregationMixin
-
-#: ``server.secure_aggregation_type`` -> ``AggregationRound.launch_robust`` mode
-ROBUST_MODES = {"Median": "median"}
-#: ``server.secure_aggregation_type`` -> f of ``AggregationRound.launch_multi_krum``: the reference's
-#: hard-coded ``num_attackers_selected`` (aggregations.py:180)
-MULTI_KRUM = {"Multi-krum": 2}
 
 
 def _secure_aggregation_type():
@@ -41,12 +35,44 @@ def _secure_aggregation_type():
         return None
 
 
+def _num_attackers() -> int:
+    """``len(Config().clients.attacker_ids)``, as ``aggregations.bulyan`` reads it (aggregations.py:80)."""
+    from plato.config import Config
+
+    return len(Config().clients.attacker_ids)
+
+
+# An aggregator takes the server and returns the launch on the staged round.  It reads what it needs from
+# the server before the engine is touched: a missing ``Config`` fails with nothing staged.
+def _median(server):
+    return lambda rnd: rnd.launch_robust("median")
+
+
+def _multi_krum(server):
+    return lambda rnd: rnd.launch_multi_krum(2)  # the reference's hard-coded num_attackers_selected (aggregations.py:180)
+
+
+def _bulyan(server):
+    f = int(server.num_attackers) if server.num_attackers is not None else _num_attackers()
+    return lambda rnd: rnd.launch_bulyan(f)
+
+
+def _trimmed_mean(server):
+    return lambda rnd: rnd.launch_robust("nearest_mean", int(server.trim))
+
+
+def _fl_trust(server):
+    return lambda rnd: rnd.launch_fltrust()
+
+
 class RobustAggregationMixin(FusedAggregationMixin):
     """``aggregate_weights`` hook of the detector server: "Median" and "Multi-krum" on the GPU, else the
     fused FedAvg."""
 
     #: None = ``Config().server.secure_aggregation_type`` (absent: FedAvg, as in the reference)
     secure_aggregation_type = None
+    #: ``server.secure_aggregation_type`` -> aggregator; a subclass extends its parent's
+    aggregators = {"Median": _median, "Multi-krum": _multi_krum}
 
     def robust_aggregation_type(self):
         own = self.secure_aggregation_type
@@ -56,15 +82,16 @@ class RobustAggregationMixin(FusedAggregationMixin):
         name = self.robust_aggregation_type()
         if name is None:  # the reference's "Fedavg is applied" branch
             return await super().aggregate_weights(updates, baseline_weights, weights_received)
-        if name not in ROBUST_MODES and name not in MULTI_KRUM:
+        if name not in self.aggregators:
             raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
-                             f"(supported: {', '.join(sorted({**ROBUST_MODES, **MULTI_KRUM}))})")
+                             f"(supported: {', '.join(sorted(self.aggregators))})")
         codec = payload_codec(weights_received[0])
         if codec != "native":
             raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
         engine = self.aggregation_engine()
         if getattr(engine, "primary", None) is not None:
             raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
+        launch = self.aggregators[name](self)
         try:
             rnd = engine.begin(weights_received[0], len(weights_received))
 
@@ -76,25 +103,11 @@ class RobustAggregationMixin(FusedAggregationMixin):
 
             await self._off_loop(stage)
             with tracing.range("plato_amd.launch"):
-                if name in MULTI_KRUM:
-                    rnd.launch_multi_krum(MULTI_KRUM[name])
-                else:
-                    rnd.launch_robust(ROBUST_MODES[name])
+                launch(rnd)
             with tracing.range("plato_amd.fetch"):
                 return await self._finish(rnd)
         finally:
             engine.release_arrivals()
-
-
-#: the names :class:`DetectorAggregationMixin` handles itself
-DETECTOR_MODES = ("Bulyan", "Trimmed-mean")
-
-
-def _num_attackers() -> int:
-    """``len(Config().clients.attacker_ids)``, as ``aggregations.bulyan`` reads it (aggregations.py:80)."""
-    from plato.config import Config
-
-    return len(Config().clients.attacker_ids)
 
 
 class DetectorAggregationMixin(RobustAggregationMixin):
@@ -114,45 +127,7 @@ class DetectorAggregationMixin(RobustAggregationMixin):
     #: None = ``len(Config().clients.attacker_ids)``
     num_attackers = None
     trim = 0
-
-    async def aggregate_weights(self, updates, baseline_weights, weights_received):
-        name = self.robust_aggregation_type()
-        if name not in DETECTOR_MODES:
-            if name is not None and name not in ROBUST_MODES and name not in MULTI_KRUM:  # the parent's refusal, this list
-                raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
-                                 f"(supported: {', '.join(sorted({*ROBUST_MODES, *MULTI_KRUM, *DETECTOR_MODES}))})")
-            return await super().aggregate_weights(updates, baseline_weights, weights_received)
-        codec = payload_codec(weights_received[0])
-        if codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
-        engine = self.aggregation_engine()
-        if getattr(engine, "primary", None) is not None:
-            raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
-        if name == "Bulyan":
-            f = int(self.num_attackers) if self.num_attackers is not None else _num_attackers()
-        try:
-            rnd = engine.begin(weights_received[0], len(weights_received))
-
-            def stage():
-                with tracing.range("plato_amd.stage"):
-                    for slot, payload in enumerate(weights_received):
-                        if not rnd.adopt(slot, payload):
-                            rnd.put_client(slot, payload)
-
-            await self._off_loop(stage)
-            with tracing.range("plato_amd.launch"):
-                if name == "Bulyan":
-                    rnd.launch_bulyan(f)
-                else:
-                    rnd.launch_robust("nearest_mean", int(self.trim))
-            with tracing.range("plato_amd.fetch"):
-                return await self._finish(rnd)
-        finally:
-            engine.release_arrivals()
-
-
-#: the name :class:`TrustAggregationMixin` handles itself
-TRUST_MODES = ("Fl-trust",)
+    aggregators = {**RobustAggregationMixin.aggregators, "Bulyan": _bulyan, "Trimmed-mean": _trimmed_mean}
 
 
 class TrustAggregationMixin(DetectorAggregationMixin):
@@ -160,34 +135,4 @@ class TrustAggregationMixin(DetectorAggregationMixin):
     every other name is the parent's.  With it every working aggregator of that example runs on the GPU
     ("Krum" and "Afa" have no behaviour to match: INTEGRATION.md §12)."""
 
-    async def aggregate_weights(self, updates, baseline_weights, weights_received):
-        name = self.robust_aggregation_type()
-        if name not in TRUST_MODES:
-            if (name is not None and name not in ROBUST_MODES and name not in MULTI_KRUM
-                    and name not in DETECTOR_MODES):  # the parents' refusal, this list
-                supported = sorted({*ROBUST_MODES, *MULTI_KRUM, *DETECTOR_MODES, *TRUST_MODES})
-                raise ValueError(f"secure_aggregation_type {name!r} is not supported on the GPU "
-                                 f"(supported: {', '.join(supported)})")
-            return await super().aggregate_weights(updates, baseline_weights, weights_received)
-        codec = payload_codec(weights_received[0])
-        if codec != "native":
-            raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
-        engine = self.aggregation_engine()
-        if getattr(engine, "primary", None) is not None:
-            raise NotImplementedError("robust aggregation runs on one GPU (aggregation_devices has several)")
-        try:
-            rnd = engine.begin(weights_received[0], len(weights_received))
-
-            def stage():
-                with tracing.range("plato_amd.stage"):
-                    for slot, payload in enumerate(weights_received):
-                        if not rnd.adopt(slot, payload):
-                            rnd.put_client(slot, payload)
-
-            await self._off_loop(stage)
-            with tracing.range("plato_amd.launch"):
-                rnd.launch_fltrust()
-            with tracing.range("plato_amd.fetch"):
-                return await self._finish(rnd)
-        finally:
-            engine.release_arrivals()
+    aggregators = {**DetectorAggregationMixin.aggregators, "Fl-trust": _fl_trust}
