@@ -265,6 +265,12 @@ int plato_agg_fedavg_entrywise(const float* const* d_x_f32, const int64_t* const
  * first n - n%8 elements, lanes added in order, tail fma'd, fp32 sqrt), so
  * the fp32 result equals the reference's bit for bit:
  *   d_out[i * n_entries + entry] = norm(d_i restricted to entry)
+ * A one-element entry (any shape with numel == 1, () included) gives |d|, as
+ * torch does: no square is formed, so |d| below 1.1e-19 or above 1.8e19 comes
+ * back as it is where sqrt(d * d) would give 0, a rounded value or inf.  From
+ * two elements on NaN, +-inf, subnormal squares and sums that overflow follow
+ * the chain's IEEE arithmetic (pinned at such values against torch through
+ * oracle/reductions.c: tests/test_reductions.py, tests/test_special_values_gpu.py).
  * d_entries_* hold ONE piece per entry (ArenaLayout.chunk_tables(2**32)), in
  * any order: the table order is the dispatch order, and since each norm is one
  * serial chain, passing the longest entries first shortens the launch (the
@@ -396,6 +402,11 @@ int plato_agg_flatten(int mode, const void* const* d_src_f32, const void* const*
  * sdot_k_SKYLAKEX (the x86-64 AVX-512 kernel; cblas_sdot calls it unthreaded):
  * FedAdp's inner products and norms (fedadp_server.py:95-99; np.linalg.norm
  * is sqrt of the float32 self dot).  Vectors 16-byte aligned.
+ * n == 1: the kernels return +0 + x[0] * y[0], numpy the bare product, so a
+ * product of -0 comes back as +0 here and as -0 there (equal by value; the
+ * only departure, and only in the sign of zero).  FedAdp, the one consumer,
+ * takes arccos(clip(inner / norms)), which gives the same bits for both zeros.
+ * The same holds for plato_agg_sdot_shared and plato_agg_fedadp_dots.
  */
 int plato_agg_sdot_pairs(const float* const* d_x, const float* const* d_y, int n_pairs, size_t n,
                          float* d_out_xy, float* d_out_yy, hipStream_t stream);
@@ -468,7 +479,9 @@ int plato_agg_fedadp_dots_ex(const float* d_x, const void* const* d_src_f32, con
  * PLATO_AGG_PORT_CAST_FIRST for vector 0, current - previous, the difference
  * of the two casts); d_out[v] = torch.linalg.vector_norm of it in x86-64
  * ATen's order (8 fma chains over n - n % 8 positions, the lanes added in
- * order, the scalar tail).  d_x_f32 / d_x_i64 / d_b_f32 / d_b_i64: n_vectors
+ * order, the scalar tail); a vector of one position (n_flat == 1 or
+ * d_lengths[v] == 1) gives |d|, as torch does for a one-element tensor (no
+ * square, see plato_agg_entry_norms_f32).  d_x_f32 / d_x_i64 / d_b_f32 / d_b_i64: n_vectors
  * device pointers each (arenas of n_f32 fp32 elements / the int64 counters).
  * d_flat_out: null, or n_vectors 16-byte aligned rows of >= n_flat floats that
  * receive the flattened vectors (what plato_agg_torch_cosine_sum then reads).

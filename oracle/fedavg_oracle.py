@@ -362,9 +362,13 @@ def torch_cpu_norm_f32(rows: np.ndarray) -> np.ndarray:
     products added in order if 4+ remain, the last 1-3 fma'd; fp32 sqrt.
     (The fma below is emulated in float64: exact product, one rounding of the
     sum to float64, then to float32 — double rounding can flip a last bit in
-    rare ties; oracle/reductions.c has the exact fmaf version.)"""
+    rare ties; oracle/reductions.c has the exact fmaf version.)
+    One-element rows (torch: any shape with numel == 1) are ``|x|``, with no
+    square that could underflow or overflow."""
     rows = np.asarray(rows, dtype=np.float32)
     k, n = rows.shape
+    if n == 1:
+        return np.abs(rows[:, 0])
     m = n - n % 8
     acc = np.zeros((k, 8), dtype=np.float32)
     blocks = rows[:, :m].reshape(k, -1, 8).astype(np.float64)

@@ -45,6 +45,8 @@
 
 /* ------------------------------------------------------------ OpenBLAS */
 float plato_oracle_sdot_skx(int64_t n, const float* x, const float* y) {
+  /* np.inner of one-element vectors never reaches cblas_sdot: the bare product, so -0 stays -0 */
+  if (n == 1) return x[0] * y[0];
   double tail = 0.0, kern = 0.0;
   const int64_t n1 = n & -32;
   if (n1) {
@@ -72,6 +74,9 @@ float plato_oracle_sdot_skx(int64_t n, const float* x, const float* y) {
 
 /* --------------------------------------------------------------- torch */
 float plato_oracle_torch_norm(const float* x, int64_t n) {
+  /* a one-element tensor (any shape with numel == 1): |x|, no square, so 1e-30 and 1e25 come back as
+   * they are where sqrt(x * x) gives 0 and inf */
+  if (n == 1) return fabsf(x[0]);
   float acc[8] = {0};
   const int64_t m = n - n % 8;
   for (int64_t d = 0; d < m; d += 8)

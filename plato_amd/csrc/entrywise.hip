@@ -534,6 +534,13 @@ __device__ __forceinline__ float torch_norm_tail_step(float s, float v, uint64_t
   return __builtin_fmaf(v, v, s);
 }
 
+// The norm's last step.  torch.linalg.norm / vector_norm of a one-element tensor (any shape with
+// numel == 1) is |x|: no square, so nothing underflows or overflows on the way.  `last` is the
+// tail's last value, the whole vector when n == 1.
+__device__ __forceinline__ float torch_norm_finish(float s, float last, uint64_t n) {
+  return n == 1 ? __builtin_fabsf(last) : sqrtf(s);
+}
+
 template <bool HAS_BASE, bool I64>
 __device__ __forceinline__ float norm_delta(const void* x, const void* b, uint64_t e) {
   if constexpr (I64) {
@@ -595,11 +602,12 @@ __device__ void norm_pair(const NormArgs& a, const Chunk ch, int i, int lane, fl
   float s = __shfl(acc, 0, 64);
   for (int l = 1; l < kNormLanes; ++l) s = s + __shfl(acc, l, 64);
   if (lane != 0) return;
+  float v = 0.f;
   for (uint64_t e = m; e < n; ++e) {
-    const float v = norm_delta<HAS_BASE, I64>(x, b, ch.begin + e);
+    v = norm_delta<HAS_BASE, I64>(x, b, ch.begin + e);
     s = torch_norm_tail_step(s, v, e, m, n);
   }
-  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = sqrtf(s);
+  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = torch_norm_finish(s, v, n);
 }
 
 // kRest: only the pairs the split register-staged launch leaves out (int64 entries, and the fp32 entry
@@ -854,7 +862,7 @@ __device__ float pc_chain(const Chunk ch, int lane, const float* dtile, int dstr
 }
 
 // The chain wave's epilogue: the 8 lanes added in order (ATen's buffer[0] + buffer[1] + ...),
-// then the scalar tail over positions m .. n - 1, then the square root.
+// then the scalar tail over positions m .. n - 1, then the square root (|d| for a one-element entry).
 template <bool HAS_BASE>
 __device__ __forceinline__ void pc_finish(const NormArgs& a, const Chunk ch, int i, const float* x, int lane,
                                           float acc) {
@@ -862,12 +870,13 @@ __device__ __forceinline__ void pc_finish(const NormArgs& a, const Chunk ch, int
   float s = __shfl(acc, 0, 64);
   for (int l = 1; l < kNormLanes; ++l) s = s + __shfl(acc, l, 64);
   if (lane != 0) return;
+  float v = 0.f;
   for (uint64_t e = m; e < n; ++e) {
     const uint64_t idx = ch.begin + e;
-    const float v = HAS_BASE ? x[idx] - a.base_f[idx] : x[idx];
+    v = HAS_BASE ? x[idx] - a.base_f[idx] : x[idx];
     s = torch_norm_tail_step(s, v, e, m, n);
   }
-  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = sqrtf(s);
+  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = torch_norm_finish(s, v, n);
 }
 
 // Long entries (at least half as long as the table's first: the engine passes the table longest
@@ -1136,12 +1145,13 @@ __device__ __forceinline__ void pc_finish_folded(const NormArgs& a, const Chunk 
   if (lane >= 8 * C || (lane & 7) || i >= a.K) return;
   const uint64_t n = ch.end - ch.begin, m = n - n % kNormLanes;
   const float* x = sld(a.xf, i);
+  float v = 0.f;
   for (uint64_t e = m; e < n; ++e) {
     const uint64_t idx = ch.begin + e;
-    const float v = HAS_BASE ? x[idx] - a.base_f[idx] : x[idx];
+    v = HAS_BASE ? x[idx] - a.base_f[idx] : x[idx];
     s = torch_norm_tail_step(s, v, e, m, n);
   }
-  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = sqrtf(s);
+  if (ch.entry < a.n_entries) a.out[uint64_t(i) * a.n_entries + ch.entry] = torch_norm_finish(s, v, n);
 }
 
 template <int T, int P, int D, int C, bool HAS_BASE, int PRIO, int kOW>

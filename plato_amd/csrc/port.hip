@@ -307,12 +307,14 @@ __global__ __launch_bounds__(64 * (1 + kWp)) void port_norms_kernel(PnArgs a_in)
   if (lane != 0) return;
   int idx = 0;
   float* flat = a.flat ? sld(a.flat, v) : nullptr;
+  float d = 0.f;
   for (uint32_t e = a.m; e < a.n; ++e) {
-    const float d = pn_value(a, S, idx, e, v);
+    d = pn_value(a, S, idx, e, v);
     if (flat) flat[e] = d;
     s = pn_tail_step(s, d, e, a.m, a.n);
   }
-  a.out[v] = sqrtf(s);
+  // a one-element vector (n_flat or d_lengths[v] == 1): torch's vector_norm is |d|, without the square
+  a.out[v] = a.n == 1 ? __builtin_fabsf(d) : sqrtf(s);
 }
 
 using PnFn = void (*)(const PnArgs&, hipStream_t, int);

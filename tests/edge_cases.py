@@ -417,3 +417,36 @@ def guarded(n: int, sentinel, dev):
 
 def fetch(t, dtype) -> np.ndarray:
     return t.cpu().numpy().view(dtype)
+
+
+def device_dots(c: dict, dev) -> np.ndarray:
+    """The 2K+1 doubles of plato_agg_client_dots on a case of dots_case: two calls that must agree bitwise,
+    sentinel-filled outputs and workspace with guards behind them."""
+    import torch
+
+    from plato_amd import _lib
+
+    k, n_f, n_i, has_base = c["k"], c["n_f"], c["n_i"], c["has_base"]
+    keep_f, pf = device_rows(c["x"], dev)
+    keep_i, pi = device_rows(c["xi"], dev)
+    tf, ti = pointer_table(pf, dev), pointer_table(pi, dev)
+    b, bi = device_array(c["b"], dev), device_array(c["bi"], dev)
+    v, vi = device_array(c["v"], dev), device_array(c["vi"], dev)
+    ws_bytes = _lib.lib().plato_agg_client_dots_workspace(k, n_f)
+    assert ws_bytes % 8 == 0 and ws_bytes >= (2 * k + 1) * 8
+    outs = []
+    for _ in range(2):
+        ws = guarded(ws_bytes // 8, SENTINEL64, dev)
+        out = guarded(2 * k + 1, SENTINEL64, dev)
+        _lib.call("plato_agg_client_dots", tf.data_ptr(), ti.data_ptr() if n_i else None, k,
+                  b.data_ptr() if has_base else None, bi.data_ptr() if has_base and n_i else None, v.data_ptr(),
+                  vi.data_ptr() if n_i else None, n_f, n_i, ws.data_ptr(), out.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize()
+        got, got_ws = fetch(out, np.uint64), fetch(ws, np.uint64)
+        assert (got[2 * k + 1:] == SENTINEL64).all(), "guard doubles behind d_out overwritten"
+        assert (got_ws[ws_bytes // 8:] == SENTINEL64).all(), "guard doubles behind the workspace overwritten"
+        assert not (got[:2 * k + 1] == SENTINEL64).any(), "an output was not written"
+        outs.append(got[:2 * k + 1].copy())
+    assert outs[0].tobytes() == outs[1].tobytes(), "two calls on the same inputs differ"
+    return outs[0].view(np.float64)

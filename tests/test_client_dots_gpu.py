@@ -27,31 +27,7 @@ DEV = torch.device("cuda:0")
 
 
 def device_dots(c: dict) -> np.ndarray:
-    """The 2K+1 doubles of plato_agg_client_dots on a case of edge_cases.dots_case."""
-    k, n_f, n_i, has_base = c["k"], c["n_f"], c["n_i"], c["has_base"]
-    keep_f, pf = E.device_rows(c["x"], DEV)
-    keep_i, pi = E.device_rows(c["xi"], DEV)
-    tf, ti = E.pointer_table(pf, DEV), E.pointer_table(pi, DEV)
-    b, bi = E.device_array(c["b"], DEV), E.device_array(c["bi"], DEV)
-    v, vi = E.device_array(c["v"], DEV), E.device_array(c["vi"], DEV)
-    ws_bytes = _lib.lib().plato_agg_client_dots_workspace(k, n_f)
-    assert ws_bytes % 8 == 0 and ws_bytes >= (2 * k + 1) * 8
-    outs = []
-    for _ in range(2):
-        ws = E.guarded(ws_bytes // 8, E.SENTINEL64, DEV)
-        out = E.guarded(2 * k + 1, E.SENTINEL64, DEV)
-        _lib.call("plato_agg_client_dots", tf.data_ptr(), ti.data_ptr() if n_i else None, k,
-                  b.data_ptr() if has_base else None, bi.data_ptr() if has_base and n_i else None, v.data_ptr(),
-                  vi.data_ptr() if n_i else None, n_f, n_i, ws.data_ptr(), out.data_ptr(),
-                  torch.cuda.current_stream(DEV).cuda_stream)
-        torch.cuda.synchronize()
-        got, got_ws = E.fetch(out, np.uint64), E.fetch(ws, np.uint64)
-        assert (got[2 * k + 1:] == E.SENTINEL64).all(), "guard doubles behind d_out overwritten"
-        assert (got_ws[ws_bytes // 8:] == E.SENTINEL64).all(), "guard doubles behind the workspace overwritten"
-        assert not (got[:2 * k + 1] == E.SENTINEL64).any(), "an output was not written"
-        outs.append(got[:2 * k + 1].copy())
-    assert outs[0].tobytes() == outs[1].tobytes(), "two calls on the same inputs differ"
-    return outs[0].view(np.float64)
+    return E.device_dots(c, DEV)
 
 
 def _shapes():
