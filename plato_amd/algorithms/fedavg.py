@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ..arrivals import adopt_or_put
 from ..engine import FedAvgEngine
 
 
@@ -129,9 +130,7 @@ class FedAttAlgorithmMixin(_AlgorithmEngine):
 
             def stage_and_norms():
                 rnd.put_baseline(baseline_weights)
-                for slot, payload in enumerate(weights_received):
-                    if not rnd.adopt(slot, payload):
-                        rnd.put_client(slot, payload)
+                adopt_or_put(rnd, weights_received)
                 # coded payloads (bf16 / QSGD): the dequantized rows, every entry float32 as the
                 # reference's inbound processor hands them over; native: the round itself
                 work = rnd.decoded()

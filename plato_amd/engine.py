@@ -30,8 +30,9 @@ import torch
 
 from . import _lib
 from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, same_f32_bits
+from .arrivals import Adopt, ArrivalTable, adopt_rule
 from .robust import RobustAggregates, RobustLaunches
-from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key, payload_fingerprint
+from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
 
 
 def fp32_weights(values: Sequence[float]) -> np.ndarray:
@@ -177,39 +178,43 @@ class FedAvgEngine(RobustAggregates):
         self._stagers: dict[str, _Stager] = {}
         self._base: DeviceArena | None = None
         self._copy_stream: torch.cuda.Stream | None = None
+        self._side: torch.cuda.Stream | None = None
         self._slab: ClientSlab | None = None      # slab of the current round's codec
         self._stager: _Stager | None = None       # native-dtype stager (baselines)
-        self._arrivals: dict = {}                 # id(payload) -> staged arrival row
-        self._arrival_free: dict = {}
+        self._arrivals = ArrivalTable()           # id(payload) -> Arrival; rows: its (fp32, int64) row pointers
         self._arrival_slabs: dict = {}
+        self._arrival_base: DeviceArena | None = None  # the model arrivals are turned into deltas against
 
     # ----------------------------------------------------------- allocation
     def _prepare(self, template: Mapping[str, torch.Tensor], k: int, codec: str = "native") -> ArenaLayout:
         if codec not in CODECS:
             raise ValueError(f"unknown payload codec {codec!r}")
-        layout = ArenaLayout.from_state_dict(template, align=self.layout_align)
-        if self._layout is None or self._layout.signature != layout.signature:
-            self._layout = layout
-            self._slabs = {}
-            self._stagers = {}
-            self._base = None
-            self._arrivals, self._arrival_free, self._arrival_slabs = {}, {}, {}
-        layout = self._layout
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(self.device)
+        layout = self._use_layout(ArenaLayout.from_state_dict(template, align=self.layout_align), codec)
         slab = self._slabs.get(codec)
         if slab is None or slab.capacity < k:
             self._slabs.pop(codec, None)
             slab = ClientSlab(layout, k, self.device, codec)
             self._slabs[codec] = slab
-        for c in {"native", codec}:
-            if c not in self._stagers:
-                self._stagers[c] = _Stager(layout, self.device, codec=c, stream=self._copy_stream)
         if self._base is None:
             self._base = DeviceArena(layout, self.device)
         self._slab = slab
         self._stager = self._stagers["native"]
         return layout
+
+    def _use_layout(self, layout: ArenaLayout, codec: str) -> ArenaLayout:
+        """The engine's layout: ``layout`` if its signature is new (arenas, stagers and arrivals of the old
+        one are dropped), with the copy stream and the native and ``codec`` stagers in place."""
+        if self._layout is None or self._layout.signature != layout.signature:
+            self._layout = layout
+            self._slabs, self._stagers, self._base = {}, {}, None
+            self._arrivals.reset()
+            self._arrival_slabs, self._arrival_base = {}, None
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(self.device)
+        for c in {"native", codec}:
+            if c not in self._stagers:
+                self._stagers[c] = _Stager(self._layout, self.device, codec=c, stream=self._copy_stream)
+        return self._layout
 
     def _upload_weights(self, weights: Sequence[float], scales: Sequence[float] | None):
         w = torch.from_numpy(fp32_weights(weights)).to(self.device, non_blocking=False)
@@ -268,10 +273,9 @@ class FedAvgEngine(RobustAggregates):
     norms_long_threshold: int | None = None
 
     def side_stream(self) -> torch.cuda.Stream:
-        st = getattr(self, "_side", None)
-        if st is None:
-            st = self._side = torch.cuda.Stream(self.device)
-        return st
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        return self._side
 
     def _norm_tables_without(self, layout: ArenaLayout, drop: tuple) -> torch.Tensor:
         """The fp32 norm table (longest first) without the entries in ``drop``."""
@@ -308,96 +312,61 @@ class FedAvgEngine(RobustAggregates):
     # ---------------------------------------------------- arrival staging
     ARRIVAL_CHUNK = 16  # rows per arrival slab; rows never move once staged
 
+    def _grow_arrivals(self, codec: str) -> list:
+        slab = ClientSlab(self._layout, self.ARRIVAL_CHUNK, self.device, codec)
+        self._arrival_slabs.setdefault(codec, []).append(slab)
+        return [(slab, r) for r in range(self.ARRIVAL_CHUNK)]
+
     def prestage(self, payload: Mapping[str, torch.Tensor], baseline_layout: ArenaLayout,
                  baseline: Mapping[str, torch.Tensor] | None = None) -> bool:
         """Copy one arriving payload to HBM now (H2D overlaps the other clients' arrival).
 
-        The next aggregation round adopts it by identity (``AggregationRound.adopt``);
-        the payload must not be modified after arrival.  Returns False if the
-        payload does not fit the layout (it is then staged at aggregation time).
-        With :attr:`delta_arenas` and the server's current model as ``baseline`` (the
-        baseline of the round this payload will join), the row is turned into its delta
-        right behind its H2D; a round adopts it only if its own baseline is that model
-        unchanged (:func:`baseline_key`), else it stages the payload again.
+        The next aggregation round adopts it by identity (``AggregationRound.adopt``; the bookkeeping is
+        ``plato_amd.arrivals``); the payload must not be modified after arrival.  Returns False if the
+        payload does not fit the layout (it is then staged at aggregation time).  With :attr:`delta_arenas`
+        and the server's current model as ``baseline`` (the baseline of the round this payload will join),
+        the row is turned into its delta right behind its H2D; a round adopts it only if its own baseline
+        is that model unchanged (``arrivals.adopt_rule``), else it stages the payload again.
         """
         codec = payload_codec(payload)
         try:
             baseline_layout.check_compatible(payload, "arriving payload", codec)
         except (KeyError, ValueError):
             return False
-        if self._layout is None or self._layout.signature != baseline_layout.signature:
-            self._layout = baseline_layout
-            self._slabs, self._stagers, self._base = {}, {}, None
-            self._arrivals, self._arrival_free, self._arrival_slabs = {}, {}, {}
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(self.device)
-        for c in {codec, "native"}:
-            if c not in self._stagers:
-                self._stagers[c] = _Stager(self._layout, self.device, codec=c, stream=self._copy_stream)
-        free = self._arrival_free.setdefault(codec, [])
-        if not free:
-            slabs = self._arrival_slabs.setdefault(codec, [])
-            slab = ClientSlab(self._layout, self.ARRIVAL_CHUNK, self.device, codec)
-            slabs.append(slab)
-            free.extend((slab, r) for r in range(self.ARRIVAL_CHUNK))
-        slab, row = free.pop()
+        self._use_layout(baseline_layout, codec)
+        slab, row = self._arrivals.take(codec, lambda: self._grow_arrivals(codec))
         self._stagers[codec].put(payload, slab.f32[row], slab.i64[row])
-        pf, pi = slab.row_pointers([row])
+        pf, pi = (int(p[0]) for p in slab.row_pointers([row]))
         delta_key = None
         if self.delta_arenas and codec == "native" and baseline is not None:
-            delta_key = self._arrival_baseline(baseline)
+            delta_key = self._arrivals.baseline(baseline, self._layout, self._stage_arrival_base)
             if delta_key is not None:  # x - b in place, behind this payload's H2D on the copy stream
-                n_i = self._layout.n_i64
-                _lib.call("plato_agg_compute_deltas", int(pf[0]), int(pi[0]) if n_i else None,
-                          _ptr(self._arrival_base.f32), _ptr(self._arrival_base.i64) if n_i else None, int(pf[0]),
-                          int(pi[0]) if n_i else None, self._layout.n_f32, n_i, _stream_handle(self._copy_stream))
-        # keep the dict alive: its id() is the key; the fingerprint detects later edits
-        self._arrivals[id(payload)] = (payload, codec, self._layout.signature, int(pf[0]), int(pi[0]), slab, row,
-                                       payload_fingerprint(payload), delta_key)
+                self._to_delta(pf, pi, self._arrival_base, self._copy_stream)
+        self._arrivals.file(payload, codec, self._layout.signature, (pf, pi), (slab, row), delta_key)
         return True
 
-    def _arrival_baseline(self, baseline: Mapping[str, torch.Tensor]):
-        """The arrival baseline on the device (staged once per model version); its key, or None."""
-        key = baseline_key(baseline)
-        if key is None:  # a model without version counters: arrivals stay weights
-            return None
-        if key == getattr(self, "_arrival_base_key", None):
-            return key
-        try:
-            self._layout.check_compatible(baseline, "baseline")
-        except (KeyError, ValueError):
-            return None
-        if getattr(self, "_arrival_base", None) is None or self._arrival_base_layout is not self._layout:
-            self._arrival_base = DeviceArena(self._layout, self.device)
-            self._arrival_base_layout = self._layout
-        # stream order on the copy stream: rows converted against the previous model ran before this copy
-        self._stagers["native"].put(baseline, self._arrival_base.f32, self._arrival_base.i64)
-        self._arrival_base_key = key
-        return key
+    def _to_delta(self, pf: int, pi: int, base: DeviceArena, stream: torch.cuda.Stream) -> None:
+        """The row at (``pf``, ``pi``) becomes x - ``base``, in place, on ``stream`` (behind the row's H2D)."""
+        lay = base.layout
+        n_i = lay.n_i64
+        _lib.call("plato_agg_compute_deltas", pf, pi if n_i else None, _ptr(base.f32), _ptr(base.i64) if n_i else None,
+                  pf, pi if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
 
-    def _arrival_rows(self, payload, layout: ArenaLayout, codec: str):
-        hit = self._arrivals.get(id(payload))
-        if hit is None or hit[0] is not payload or hit[1] != codec or hit[2] != layout.signature:
-            return None
-        if hit[7] != payload_fingerprint(payload):
-            return None  # an entry was replaced or written after arrival: stage the current tensors
-        return hit[3], hit[4], hit[8]
+    def _stage_arrival_base(self, model: Mapping[str, torch.Tensor]) -> None:
+        """``model`` as the arrival baseline on the device (``ArrivalTable.baseline``: once per model version)."""
+        if self._arrival_base is None:
+            self._arrival_base = DeviceArena(self._layout, self.device)
+        self._stagers["native"].put(model, self._arrival_base.f32, self._arrival_base.i64)
 
     def drop_arrival(self, payload) -> None:
         """Return one payload's arrival slot (a multi-GPU prestage that failed on another device).
 
         A copy still in flight into the row is ordered before any later copy into it (one copy stream)."""
-        hit = self._arrivals.pop(id(payload), None)
-        if hit is not None and hit[0] is payload:
-            self._arrival_free.setdefault(hit[1], []).append((hit[5], hit[6]))
-        elif hit is not None:
-            self._arrivals[id(payload)] = hit
+        self._arrivals.drop(payload)
 
     def release_arrivals(self) -> None:
         """Return every arrival slot (after the round that used them has completed, or failed)."""
-        for payload, codec, _, _, _, slab, row, _, _ in self._arrivals.values():
-            self._arrival_free.setdefault(codec, []).append((slab, row))
-        self._arrivals = {}
+        self._arrivals.release()
 
     # ------------------------------------------------------ raw device call
     def launch_fedavg(self, layout: ArenaLayout, ptr_f32: torch.Tensor, ptr_i64: torch.Tensor | None,
@@ -660,6 +629,9 @@ class AggregationRound(RobustLaunches):
         # final update adds the baseline once (plato_agg_update_weights: b + acc, the fused epilogue's sum).
         self.deltas = bool(getattr(engine, "delta_arenas", False)) and codec == "native"
         self._converted: set = set()
+        self._robust = False           # set by the robust launches: no baseline, every entry comes back fp32
+        self._base_key = None          # baseline_key of the staged baseline
+        self._arrival_base_ok = None   # the device check of the arrival baseline, once per round
 
     def _to_delta(self, slot: int) -> None:
         """Turn staged slot ``slot`` into its delta x - b, in place, on the copy stream (after its H2D)."""
@@ -668,12 +640,7 @@ class AggregationRound(RobustLaunches):
         key = (self._pf[slot], self._pi[slot])
         if key in self._converted:
             return
-        eng, lay = self.engine, self.layout
-        n_i = lay.n_i64
-        cs = self.stager.stream
-        _lib.call("plato_agg_compute_deltas", self._pf[slot], self._pi[slot] if n_i else None, _ptr(self._base.f32),
-                  _ptr(self._base.i64) if n_i else None, self._pf[slot], self._pi[slot] if n_i else None,
-                  lay.n_f32, n_i, _stream_handle(cs))
+        self.engine._to_delta(*key, self._base, self.stager.stream)
         self._converted.add(key)
 
     def _raw_only(self, what: str) -> None:
@@ -732,24 +699,20 @@ class AggregationRound(RobustLaunches):
         self._mv[slot] = payload.max_v_array(self.layout.keys())
 
     def adopt(self, slot: int, payload: Mapping[str, torch.Tensor]) -> bool:
-        """Use ``payload``'s copy already staged at arrival (``FedAvgEngine.prestage``), if any.
-
-        Returns False (nothing done) when the payload was not prestaged for
-        this round's layout and codec; the caller then stages it with put_client.
-        """
+        """Use ``payload``'s copy already staged at arrival (``FedAvgEngine.prestage``), if any.  Returns False
+        (nothing done) when there is none this round may use; the caller then stages it with put_client."""
         if not 0 <= slot < self.capacity:
             raise IndexError(f"slot {slot} outside [0, {self.capacity})")
-        hit = self.engine._arrival_rows(payload, self.layout, self.codec)
-        if hit is None:
+        rec = self.engine._arrivals.lookup(payload, self.codec, self.layout.signature)
+        if rec is None:
             return False
-        pf, pi, delta_key = hit
-        if delta_key is not None and not (self.deltas and delta_key == getattr(self, "_base_key", None)
-                                          and self._arrival_base_matches()):
+        how = adopt_rule(rec.delta_key, self.deltas, self.has_baseline, self._base_key, self._arrival_base_matches)
+        if how is Adopt.REFUSE:
             return False  # a delta against another model (or a weight round): stage the payload again
         self._coded_scales(slot, payload)
-        self._pf[slot], self._pi[slot] = pf, pi
-        if delta_key is not None:
-            self._converted.add((pf, pi))  # turned into its delta at arrival, against this round's baseline
+        self._pf[slot], self._pi[slot] = rec.rows
+        if how is Adopt.AS_FORMED:
+            self._converted.add(rec.rows)  # turned into its delta at arrival, against this round's baseline
         elif self.deltas:  # the arrival row holds the weights: its delta now, in place (the row is this round's)
             self._to_delta(slot)
         self.staged[slot] = True
@@ -757,27 +720,20 @@ class AggregationRound(RobustLaunches):
         return True
 
     def _arrival_base_matches(self) -> bool:
-        """The model the arrivals were turned into deltas against has this round's baseline bits.
-
-        The keys (storage + version counters) already match; an in-place write that leaves the
-        counters alone (``.data`` writes in a hook) or a freed storage reused at the same address
-        would still let a stale delta in, so the two staged arenas are compared once per round on
-        the device, after both copies (copy stream).  A mismatch makes every arrival row of the
-        round staged again from its host tensors.
-        """
-        ok = getattr(self, "_arrival_base_ok", None)
-        if ok is None:
+        """The model the arrivals were turned into deltas against has this round's baseline bits
+        (``arrivals.adopt_rule``'s ``same_bits``): the two staged arenas compared once per round on the
+        device, after both copies (copy stream).  A mismatch makes the round stage its arrivals again."""
+        if self._arrival_base_ok is None:
             eng, lay = self.engine, self.layout
-            arr = getattr(eng, "_arrival_base", None)
-            if arr is None or eng._arrival_base_layout.signature != lay.signature:
-                ok = False
+            arr = eng._arrival_base
+            if arr is None or arr.layout.signature != lay.signature:
+                self._arrival_base_ok = False
             else:
-                stream = torch.cuda.current_stream(eng.device)
-                stream.wait_stream(eng._copy_stream)
-                ok = (same_f32_bits(self._base.f32[: lay.n_f32], arr.f32[: lay.n_f32], lay.f32_padding(eng.device))
-                      and torch.equal(self._base.i64[: lay.n_i64], arr.i64[: lay.n_i64]))
-            self._arrival_base_ok = ok
-        return ok
+                torch.cuda.current_stream(eng.device).wait_stream(eng._copy_stream)
+                self._arrival_base_ok = (
+                    same_f32_bits(self._base.f32[: lay.n_f32], arr.f32[: lay.n_f32], lay.f32_padding(eng.device))
+                    and torch.equal(self._base.i64[: lay.n_i64], arr.i64[: lay.n_i64]))
+        return self._arrival_base_ok
 
     def launch(self, weights: Sequence[float], scales: Sequence[float] | None = None,
                order: Sequence[int] | None = None, deltas: bool = False) -> None:
@@ -1470,7 +1426,7 @@ class AggregationRound(RobustLaunches):
 
     def algorithmic_bytes(self) -> int:
         """HBM bytes of the launch: K client arenas + baseline read, result written."""
-        if getattr(self, "_robust", False):  # no baseline; the counters come back as fp32
+        if self._robust:  # no baseline; the counters come back as fp32
             lay = self.layout
             return (self._k + 1) * lay.n_f32_data * 4 + self._k * lay.n_i64 * 8 + lay.n_i64 * 4
         return self.layout.algorithmic_bytes(self._k)
@@ -1512,6 +1468,8 @@ class _DecodedRound(AggregationRound):
         self._mv = [None] * parent.capacity
         self._level = None
         self.has_baseline = True
+        self._base_key = self._arrival_base_ok = None
+        self._robust = False
         self.event = None
         self._out = None
         self._t0 = parent._t0

@@ -49,9 +49,10 @@ import torch
 
 from . import _lib
 from .arena import CODECS, ArenaLayout, payload_codec, same_f32_bits
+from .arrivals import Adopt, ArrivalTable, adopt_or_put, adopt_rule
 from .distributed import BucketPlan, EntryPlan
 from .engine import FedAvgEngine, fp32_weights, require_device
-from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key, payload_fingerprint
+from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
 
 MULTI_CODECS = ("native", "bf16")
 
@@ -79,27 +80,28 @@ class _Shard:
         self.base_i = torch.empty(max(self.ni, 1), dtype=torch.int64, device=device)
         self.slabs: dict[str, tuple[torch.Tensor, torch.Tensor]] = {}
         self.arrival_slabs: dict[str, list] = {}
+        self._arr = None  # arrival_base()
 
     def slab(self, codec: str, capacity: int):
         hit = self.slabs.get(codec)
         if hit is None or hit[0].shape[0] < capacity:
             self.slabs.pop(codec, None)
-            dt_f, dt_i = CODECS[codec]
-            hit = (torch.empty((capacity, self.per), dtype=dt_f, device=self.device),
-                   torch.empty((capacity, max(self.ni, 1)), dtype=dt_i, device=self.device))
-            self.slabs[codec] = hit
+            hit = self.slabs[codec] = self._rows(codec, capacity)
         return hit
 
-    def new_arrival_slab(self, codec: str, rows: int):
+    def _rows(self, codec: str, rows: int):
         dt_f, dt_i = CODECS[codec]
-        slab = (torch.empty((rows, self.per), dtype=dt_f, device=self.device),
+        return (torch.empty((rows, self.per), dtype=dt_f, device=self.device),
                 torch.empty((rows, max(self.ni, 1)), dtype=dt_i, device=self.device))
+
+    def new_arrival_slab(self, codec: str, rows: int):
+        slab = self._rows(codec, rows)
         self.arrival_slabs.setdefault(codec, []).append(slab)
         return slab
 
     def arrival_base(self):
         """This bucket of the model the arrivals are turned into deltas against (allocated on first use)."""
-        if getattr(self, "_arr", None) is None:
+        if self._arr is None:
             self._arr = (torch.empty(self.per, dtype=torch.float32, device=self.device),
                          torch.empty(max(self.ni, 1), dtype=torch.int64, device=self.device))
         return self._arr
@@ -108,10 +110,11 @@ class _Shard:
         """row -= base for this bucket, in place, on the copy stream (behind the row's and the base's H2D)."""
         if not (self.n or self.ni):
             return
-        _lib.call("plato_agg_compute_deltas", _ptr(row_f) if self.n else None, _ptr(row_i) if self.ni else None,
-                  _ptr(base_f) if self.n else None, _ptr(base_i) if self.ni else None,
-                  _ptr(row_f) if self.n else None, _ptr(row_i) if self.ni else None, self.n, self.ni,
-                  self.copy_stream.cuda_stream)
+        with torch.cuda.device(self.device):
+            _lib.call("plato_agg_compute_deltas", _ptr(row_f) if self.n else None, _ptr(row_i) if self.ni else None,
+                      _ptr(base_f) if self.n else None, _ptr(base_i) if self.ni else None,
+                      _ptr(row_f) if self.n else None, _ptr(row_i) if self.ni else None, self.n, self.ni,
+                      self.copy_stream.cuda_stream)
 
     def same_bits(self, a_f: torch.Tensor, a_i: torch.Tensor, b_f: torch.Tensor, b_i: torch.Tensor,
                   layout: ArenaLayout | None = None) -> bool:
@@ -130,10 +133,6 @@ class _Shard:
                 dst_f[: self.n].copy_(host_f[self.lo:self.hi], non_blocking=True)
             if self.ni:
                 dst_i[: self.ni].copy_(host_i[self.ilo:self.ihi], non_blocking=True)
-
-
-def _row_ptr(t: torch.Tensor, row: int) -> int:
-    return t.data_ptr() + row * t.stride(0) * t.element_size()
 
 
 def _copy_rows(dst: torch.Tensor, rows: Sequence[torch.Tensor]) -> None:
@@ -171,15 +170,13 @@ class MultiDeviceEngine:
         self._rings: dict[str, PinnedRing] = {}
         self._packers: dict[str, HostPacker] = {}
         self._results: ResultPool | None = None
-        self._arrivals: dict = {}
-        self._arrival_free: dict = {}
+        self._arrivals = ArrivalTable()  # id(payload) -> Arrival; rows: its per-shard (fp32 row, int64 row)
         self._comm = None
         self._entries: "EntryShardedEngine | None" = None
         self._clients: "ClientShardedEngine | None" = None
         self._client_engines: list[FedAvgEngine] = [self.primary]
         self._pool = None
         self._delta_arenas = False
-        self._arrival_base_key = None
 
     @property
     def delta_arenas(self) -> bool:
@@ -266,8 +263,7 @@ class MultiDeviceEngine:
             self._shards = [_Shard(g, d, self._plan) for g, d in enumerate(self.devices)]
             self._rings, self._packers = {}, {}
             self._results = ResultPool(layout)
-            self._arrivals, self._arrival_free = {}, {}
-            self._arrival_base_key = None
+            self._arrivals.reset()
         return self._layout
 
     def _ring(self, codec: str) -> tuple[PinnedRing, HostPacker]:
@@ -316,12 +312,8 @@ class MultiDeviceEngine:
 
     def prestage(self, payload: Mapping[str, torch.Tensor], baseline_layout: ArenaLayout,
                  baseline: Mapping[str, torch.Tensor] | None = None) -> bool:
-        """Copy an arriving payload's buckets to their GPUs now (adopted by the next round).
-
-        With :attr:`delta_arenas` and the server's current model as ``baseline``, each bucket of the
-        row is turned into its delta right behind its H2D, against that model's bucket on the same GPU
-        (FedAvgEngine.prestage, per bucket); a round adopts it only if its own baseline is that model
-        unchanged (its :func:`baseline_key`, and the staged bits compared on the device)."""
+        """Copy an arriving payload's buckets to their GPUs now (adopted by the next round): FedAvgEngine.prestage
+        per bucket, the delta against ``baseline`` formed against that model's bucket on the same GPU."""
         codec = payload_codec(payload)
         if codec not in MULTI_CODECS:
             return self.primary.prestage(payload, baseline_layout, baseline)
@@ -330,57 +322,25 @@ class MultiDeviceEngine:
         except (KeyError, ValueError):
             return False
         self._prepare(baseline_layout)
-        free = self._arrival_free.setdefault(codec, [])
-        if not free:
-            slabs = [s.new_arrival_slab(codec, self.ARRIVAL_CHUNK) for s in self._shards]
-            free.extend((slabs, r) for r in range(self.ARRIVAL_CHUNK))
-        slabs, row = free.pop()
-        self._stage(payload, codec, [(f[row], i[row]) for f, i in slabs])
+        rows = self._arrivals.take(codec, lambda: self._grow_arrivals(codec))  # per shard (fp32 row, int64 row)
+        self._stage(payload, codec, rows)
         delta_key = None
         if self._delta_arenas and codec == "native" and baseline is not None:
-            delta_key = self._arrival_baseline(baseline)
+            # the arrival baseline's buckets on their GPUs, staged once per model version
+            delta_key = self._arrivals.baseline(baseline, self._layout, lambda model: self._stage(
+                model, "native", [s.arrival_base() for s in self._shards]))
             if delta_key is not None:  # x - b per bucket, in place, behind this payload's H2D
-                for s, (f, i) in zip(self._shards, slabs):
-                    af, ai = s.arrival_base()
-                    s.to_delta(f[row], i[row], af, ai)
-        ptrs = [(_row_ptr(f, row), _row_ptr(i, row)) for f, i in slabs]
-        self._arrivals[id(payload)] = (payload, codec, self._layout.signature, ptrs, slabs, row,
-                                       payload_fingerprint(payload), delta_key)
+                for s, (f, i) in zip(self._shards, rows):
+                    s.to_delta(f, i, *s.arrival_base())
+        self._arrivals.file(payload, codec, self._layout.signature, rows, rows, delta_key)
         return True
 
-    def _arrival_baseline(self, baseline: Mapping[str, torch.Tensor]):
-        """The arrival baseline's buckets on their GPUs (staged once per model version); its key, or None."""
-        key = baseline_key(baseline)
-        if key is None:
-            return None
-        if key == self._arrival_base_key:
-            return key
-        try:
-            self._layout.check_compatible(baseline, "baseline")
-        except (KeyError, ValueError):
-            return None
-        # copy-stream order: rows converted against the previous model ran before this copy
-        self._stage(baseline, "native", [s.arrival_base() for s in self._shards])
-        self._arrival_base_key = key
-        return key
-
-    def _arrival_base_matches(self, shards_base) -> bool:
-        """The round's staged baseline (``[(base_f, base_i)]`` per shard) has the arrival baseline's bits."""
-        return all(s.same_bits(bf, bi, *s.arrival_base(), layout=self._layout)
-                   for s, (bf, bi) in zip(self._shards, shards_base))
-
-    def _arrival_rows(self, payload, layout: ArenaLayout, codec: str):
-        hit = self._arrivals.get(id(payload))
-        if hit is None or hit[0] is not payload or hit[1] != codec or hit[2] != layout.signature:
-            return None
-        if hit[6] != payload_fingerprint(payload):
-            return None  # edited after arrival: the round stages its current tensors
-        return hit[3], [(f[hit[5]], i[hit[5]]) for f, i in hit[4]], hit[7]
+    def _grow_arrivals(self, codec: str) -> list:
+        slabs = [s.new_arrival_slab(codec, self.ARRIVAL_CHUNK) for s in self._shards]
+        return [[(f[r], i[r]) for f, i in slabs] for r in range(self.ARRIVAL_CHUNK)]
 
     def release_arrivals(self) -> None:
-        for _, codec, _, _, slabs, row, _, _ in self._arrivals.values():
-            self._arrival_free.setdefault(codec, []).append((slabs, row))
-        self._arrivals = {}
+        self._arrivals.release()
         self.primary.release_arrivals()
         if self._entries is not None:
             self._entries._release()
@@ -421,9 +381,7 @@ class MultiDeviceEngine:
             return self.primary.aggregate_weights(baseline, weights_received, weights, scales)
         rnd = self.begin(baseline, k, codec)
         rnd.put_baseline(baseline)
-        for i, sd in enumerate(weights_received):
-            if not rnd.adopt(i, sd):
-                rnd.put_client(i, sd)
+        adopt_or_put(rnd, weights_received)
         rnd.launch(weights, scales)
         return rnd.result()
 
@@ -476,8 +434,8 @@ class MultiRound:
         self.capacity = capacity
         self.codec = codec
         self.staged = [False] * capacity
-        self._ptrs: list = [None] * capacity  # per slot: per shard (fp32 row ptr, int64 row ptr)
         self._rows: list = [None] * capacity  # per slot: per shard (fp32 row, int64 row) tensors
+        self._ptrs: list = [None] * capacity  # ... and their device pointers
         self.has_baseline = False
         self.events: list = []
         self._out = None
@@ -504,6 +462,8 @@ class MultiRound:
         self._arrival_base_ok = None
 
     def _to_delta(self, rows) -> None:
+        if not self.has_baseline:
+            raise ValueError("delta arenas: stage the baseline before the clients")
         key = tuple(r[0].data_ptr() for r in rows)
         if key in self._converted:
             return
@@ -518,44 +478,42 @@ class MultiRound:
         if self.deltas and not self.has_baseline:
             raise ValueError("delta arenas: stage the baseline before the clients")
         eng = self.engine
-        rows = []
-        ptrs = []
-        for s in eng._shards:
-            f, i = s.slabs[self.codec]
-            rows.append((f[slot], i[slot]))
-            ptrs.append((_row_ptr(f, slot), _row_ptr(i, slot)))
+        rows = [(f[slot], i[slot]) for f, i in (s.slabs[self.codec] for s in eng._shards)]
         eng._stage(payload, self.codec, rows)
         self._converted.discard(tuple(r[0].data_ptr() for r in rows))  # fresh weights in the rows
         if self.deltas:
             self._to_delta(rows)
-        self._ptrs[slot] = ptrs
+        self._use_rows(slot, rows)
+
+    def _use_rows(self, slot: int, rows) -> None:
         self._rows[slot] = rows
+        self._ptrs[slot] = [(f.data_ptr(), i.data_ptr()) for f, i in rows]
         self.staged[slot] = True
 
     def adopt(self, slot: int, payload) -> bool:
         if not 0 <= slot < self.capacity:
             raise IndexError(f"slot {slot} outside [0, {self.capacity})")
-        hit = self.engine._arrival_rows(payload, self.layout, self.codec)
-        if hit is None:
+        rec = self.engine._arrivals.lookup(payload, self.codec, self.layout.signature)
+        if rec is None:
             return False
-        ptrs, rows, delta_key = hit
-        if delta_key is not None:
-            if not (self.deltas and self.has_baseline and delta_key == self._base_key):
-                return False  # a delta against another model (or a weight round): stage the payload again
-            if self._arrival_base_ok is None:  # the key matched; the bits must too (an in-place write that
-                # left the version counters alone, a reused address): compared once per round, on the devices
-                self._arrival_base_ok = self.engine._arrival_base_matches([(s.base_f, s.base_i)
-                                                                            for s in self.engine._shards])
-            if not self._arrival_base_ok:
-                return False
-            self._converted.add(tuple(r[0].data_ptr() for r in rows))
+        how = adopt_rule(rec.delta_key, self.deltas, self.has_baseline, self._base_key, self._arrival_base_matches)
+        if how is Adopt.REFUSE:
+            return False  # a delta against another model (or a weight round): stage the payload again
+        if how is Adopt.AS_FORMED:
+            self._converted.add(tuple(r[0].data_ptr() for r in rec.rows))
         elif self.deltas:
-            if not self.has_baseline:
-                raise ValueError("delta arenas: stage the baseline before the clients")
-            self._to_delta(rows)  # the arrival rows hold weights: their deltas now (the rows are this round's)
-        self._ptrs[slot], self._rows[slot] = ptrs, rows
-        self.staged[slot] = True
+            self._to_delta(rec.rows)  # the arrival rows hold weights: their deltas now (the rows are this round's)
+        self._use_rows(slot, rec.rows)
         return True
+
+    def _arrival_base_matches(self) -> bool:
+        """Every shard's staged baseline has the arrival baseline's bits (AggregationRound._arrival_base_matches):
+        compared once per round, on the devices."""
+        if self._arrival_base_ok is None:
+            eng = self.engine
+            self._arrival_base_ok = all(s.same_bits(s.base_f, s.base_i, *s.arrival_base(), layout=eng._layout)
+                                        for s in eng._shards)
+        return self._arrival_base_ok
 
     def launch(self, weights: Sequence[float], scales: Sequence[float] | None = None,
                order: Sequence[int] | None = None, deltas: bool = False, gather: bool = False) -> None:
@@ -753,6 +711,7 @@ class ClientRound(MultiRound):
         super().__init__(engine, layout, capacity, codec)
         self._baseline_sd = None
         self._split = None  # [(AggregationRound on device g, {slot: local slot})]
+        self._assembly_events = None
         self.last_norms = None
 
     def put_baseline(self, baseline) -> None:
@@ -839,7 +798,7 @@ class ClientRound(MultiRound):
 
     def _resolve_assembly(self) -> None:
         """``timings["client_assembly_ms"]`` once the devices have passed the assembly (after a reduction's sync)."""
-        evs = getattr(self, "_assembly_events", None)
+        evs = self._assembly_events
         if evs and all(e1.query() for _, e1 in evs):
             self.timings["client_assembly_ms"] = max(e0.elapsed_time(e1) for e0, e1 in evs)
             self._assembly_events = None
@@ -1027,7 +986,7 @@ class EntryShardedEngine:
         for eng in self._engines:
             eng.delta_arenas = multi.delta_arenas
         self._plans: dict = {}
-        self._arrivals: dict = {}
+        self._arrivals = ArrivalTable()  # id(payload) -> Arrival; rows: the shards' sub-payloads, no slot of its own
         self._pool = None
 
     @property
@@ -1098,7 +1057,7 @@ class EntryShardedEngine:
                         self._engines[g0].drop_arrival(sub0)
                     return False
             done.append((g, sub))
-        self._arrivals[id(payload)] = (payload, payload_fingerprint(payload), subs)
+        self._arrivals.file(payload, None, None, subs)  # codec and layout are checked per shard
         return True
 
     def _sub_layout(self, layout: ArenaLayout, names) -> ArenaLayout:
@@ -1109,14 +1068,8 @@ class EntryShardedEngine:
                                                                 for n in names])
         return hit
 
-    def _arrival_subs(self, payload):
-        hit = self._arrivals.get(id(payload))
-        if hit is None or hit[0] is not payload or hit[1] != payload_fingerprint(payload):
-            return None  # not prestaged here, or edited after arrival: the round stages its current tensors
-        return hit[2]
-
     def _release(self) -> None:
-        self._arrivals = {}
+        self._arrivals.release()
         for eng in self._engines:
             eng.release_arrivals()
 
@@ -1182,7 +1135,8 @@ class EntryRound:
         self._decoded = None
 
     def adopt(self, slot: int, payload) -> bool:
-        subs = self.engine._arrival_subs(payload)
+        rec = self.engine._arrivals.lookup(payload, None, None)
+        subs = None if rec is None else rec.rows
         if subs is None or len(subs) != len(self._rounds):
             return False
         if not all(self._each(lambda i, r: r.adopt(slot, subs[i]))):

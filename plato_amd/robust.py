@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .arena import payload_codec
+from .arrivals import adopt_or_put
 
 
 class RobustLaunches:
@@ -234,9 +235,7 @@ class RobustAggregates:
             raise ValueError(f"robust aggregation takes native payloads, not {codec} codes")
         rnd = self.begin(payloads[0], k)
         rnd.deltas = False  # no baseline: the rows stay weights
-        for i, sd in enumerate(payloads):
-            if not rnd.adopt(i, sd):
-                rnd.put_client(i, sd)
+        adopt_or_put(rnd, payloads)
         return rnd
 
     def aggregate_robust(self, payloads: Sequence[Mapping[str, torch.Tensor]], mode: str = "median",

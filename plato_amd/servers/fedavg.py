@@ -27,6 +27,7 @@ import concurrent.futures
 from .. import tracing
 from .. import weights as W
 from ..arena import payload_codec
+from ..arrivals import adopt_or_put
 from ..engine import FedAvgEngine
 
 
@@ -172,10 +173,8 @@ class FusedAggregationMixin(_EngineHolder):
             def stage():
                 with tracing.range("plato_amd.stage"):
                     rnd.put_baseline(baseline_weights)
-                    for slot, payload in enumerate(weights_received):
-                        # payloads staged at arrival (WireIngestMixin.stage_on_arrival) are adopted in place
-                        if not rnd.adopt(slot, payload):
-                            rnd.put_client(slot, payload)
+                    # payloads staged at arrival (WireIngestMixin.stage_on_arrival) are adopted in place
+                    adopt_or_put(rnd, weights_received)
 
             # Pack + H2D run on a worker thread: the event loop keeps serving the
             # clients meanwhile (the reference yields per client, servers/fedavg.py:157).

@@ -61,6 +61,13 @@ class WireIngestMixin:
         except (AttributeError, TypeError):
             return None
 
+    def _stage_arrival(self, payload) -> None:
+        """With ``stage_on_arrival``: copy a natively ingested payload to HBM now, on the engine of its round."""
+        if self.stage_on_arrival and isinstance(payload, ingest.ArenaStateDict):
+            layout = self._ingest_layout()
+            if layout is not None:
+                self.round_engine(payload_codec(payload)).prestage(payload, layout, self._arrival_baseline())
+
     def ingest_payload(self, payload):
         """Native ``pickle.loads`` of one payload (falls back for non-tensor payloads).
 
@@ -106,10 +113,7 @@ class WireIngestMixin:
         checkpoint_path = Config().params["checkpoint_path"]
         payload, file_len = self._load_payload_file(f"{checkpoint_path}/{model_name}_client_{client_id}.pth")
         self.client_payload[sid] = payload
-        if self.stage_on_arrival and isinstance(payload, ingest.ArenaStateDict):
-            layout = self._ingest_layout()
-            if layout is not None:
-                self.round_engine(payload_codec(payload)).prestage(payload, layout, self._arrival_baseline())
+        self._stage_arrival(payload)
 
         if self.wire_size_accounting and file_len is not None:
             payload_size = (file_len + sys.getsizeof(b"")) / 1024**2
@@ -138,10 +142,7 @@ class WireIngestMixin:
         if sizes.get(sid) is not None:
             # the bytes this part arrived as, for the size accounting below
             sizes[sid].append(wire_len)
-        if self.stage_on_arrival and isinstance(_data, ingest.ArenaStateDict):
-            layout = self._ingest_layout()
-            if layout is not None:
-                self.round_engine(payload_codec(_data)).prestage(_data, layout, self._arrival_baseline())
+        self._stage_arrival(_data)
 
         if self.client_payload[sid] is None:
             self.client_payload[sid] = _data

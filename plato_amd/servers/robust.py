@@ -22,6 +22,7 @@ from __future__ import annotations
 
 from .. import tracing
 from ..arena import payload_codec
+from ..arrivals import adopt_or_put
 from .fedavg import FusedAggregationMixin
 
 
@@ -97,9 +98,7 @@ class RobustAggregationMixin(FusedAggregationMixin):
 
             def stage():
                 with tracing.range("plato_amd.stage"):
-                    for slot, payload in enumerate(weights_received):
-                        if not rnd.adopt(slot, payload):
-                            rnd.put_client(slot, payload)
+                    adopt_or_put(rnd, weights_received)
 
             await self._off_loop(stage)
             with tracing.range("plato_amd.launch"):

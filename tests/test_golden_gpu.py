@@ -442,15 +442,13 @@ def test_weighted_sum_matches_sequential_loop(engine):
 
 def _arrival_delta_keys(eng, kind: str, layout) -> list:
     """Per arrived payload: the key of the model its rows were turned into deltas against (None: weights)."""
-    if kind == "single":
-        return [hit[8] for hit in eng._arrivals.values()]
-    if kind in ("multi", "clients"):
-        return [hit[7] for hit in eng._arrivals.values()]
+    if kind != "entry":
+        return [rec.delta_key for rec in eng._arrivals.values()]
     ent = eng.entries
     parts = ent.plan(layout)[1]
     keys = []
-    for _, _, subs in ent._arrivals.values():
-        per = [ent._engines[g]._arrivals[id(sub)][8] for (g, _), sub in zip(parts, subs)]
+    for rec in ent._arrivals.values():
+        per = [ent._engines[g]._arrivals[id(sub)].delta_key for (g, _), sub in zip(parts, rec.rows)]
         keys.append(None if any(k is None for k in per) else tuple(per))
     return keys
 

@@ -362,7 +362,7 @@ def test_fedadp_server_with_arrival_staging_matches_reference(deltas):
     eng = server.aggregation_engine()
     assert eng.delta_arenas is deltas
     assert len(eng._arrivals) == recipe["k"]
-    assert all((hit[8] is not None) == deltas for hit in eng._arrivals.values())
+    assert all((rec.delta_key is not None) == deltas for rec in eng._arrivals.values())
     for c, u in enumerate(updates):
         u.payload = arrived[c]
     server.current_round = recipe["current_round"]
@@ -416,7 +416,7 @@ def test_delta_round_matches_weight_round(name):
                 assert eng.prestage(p, rnd.layout) and rnd.adopt(i, p)
             elif i == 2 and deltas:  # and one turned into its delta at arrival against the same model
                 assert eng.prestage(p, rnd.layout, baseline=base)
-                assert eng._arrivals[id(p)][8] is not None and rnd.adopt(i, p)
+                assert eng._arrivals[id(p)].delta_key is not None and rnd.adopt(i, p)
             else:
                 rnd.put_client(i, p)
         g_f, g_i = rnd.launch_entrywise(w1, add_base=False, device=True)

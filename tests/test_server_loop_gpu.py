@@ -145,8 +145,61 @@ def test_raising_weights_release_the_arrival_slots():
         asyncio.run(server.aggregate_weights(updates, base, pays))
     assert eng._arrivals == {}
     # the freed slots serve the next round, which sees only its own payloads
-    free = sum(len(v) for v in eng._arrival_free.values())
-    assert free >= len(pays)
+    assert eng._arrivals.free_count() >= len(pays)
+
+
+def _arrival_slab_counts(eng, engine_kind) -> list:
+    """Arrival slabs allocated so far, per place that allocates them (engine, bucket shard, entry shard)."""
+    if engine_kind == "single":
+        return [sum(len(v) for v in eng._arrival_slabs.values())]
+    if engine_kind == "multi":
+        return [sum(len(v) for v in s.arrival_slabs.values()) for s in eng._shards]
+    return [sum(len(v) for v in e._arrival_slabs.values()) for e in eng._engines]
+
+
+@pytest.mark.parametrize("deltas", [False, True], ids=["weights", "deltas"])
+@pytest.mark.parametrize("engine_kind", ["single", "multi", "entry"])
+def test_seventeen_arrivals_fill_a_second_slab_and_are_all_adopted(engine_kind, deltas):
+    """One arrival more than a slab holds (ARRIVAL_CHUNK = 16): the second slab is allocated, a round
+    adopts rows of both slabs, and the released slots serve the next 17 arrivals without a third slab."""
+    layout = ArenaLayout.from_shapes([("a", (37, 7), "f32"), ("n", (), "i64"), ("b", (3, 5), "f32")])
+    k, seed = 17, 5
+    bf, bi = synth.baseline_arena(layout.n_f32, layout.n_i64, seed)
+    xs = [synth.client_arena(bf, bi, seed, c) for c in range(k)]
+    base = layout.unpack(torch.from_numpy(bf), torch.from_numpy(bi))
+    pays = [layout.unpack(torch.from_numpy(xf), torch.from_numpy(xi)) for xf, xi in xs]
+    if engine_kind == "single":
+        eng = FedAvgEngine(DEV)
+        eng.delta_arenas = deltas
+    else:
+        from plato_amd.multi import MultiDeviceEngine
+
+        eng = MultiDeviceEngine([DEV, DEV])
+        eng.delta_arenas = deltas
+        if engine_kind == "entry":
+            eng = eng.entries
+    assert FedAvgEngine.ARRIVAL_CHUNK == 16 and k == FedAvgEngine.ARRIVAL_CHUNK + 1
+    blay = ArenaLayout.from_state_dict(base)
+    for p in reversed(pays):
+        assert eng.prestage(p, blay, base if deltas else None)
+    assert len(eng._arrivals) == k
+    counts = _arrival_slab_counts(eng, engine_kind)
+    assert set(counts) - {0} == {2}, counts
+    rnd = eng.begin(base, k)
+    rnd.put_baseline(base)
+    assert [rnd.adopt(slot, p) for slot, p in enumerate(pays)] == [True] * k
+    w = ref.fedavg_weights(synth.num_samples(k, seed))
+    rnd.launch(w)
+    got = rnd.result()
+    eng.release_arrivals()
+    assert len(eng._arrivals) == 0
+    exp_f, exp_i = ref.fedavg_numpy(bf, bi, [x[0] for x in xs], [x[1] for x in xs], w)
+    assert _flat(layout, got, "f32").tobytes() == exp_f.tobytes()
+    assert _flat(layout, got, "i64").tobytes() == exp_i.tobytes()
+    for p in reversed(pays):
+        assert eng.prestage(p, blay, base if deltas else None)
+    assert _arrival_slab_counts(eng, engine_kind) == counts
+    eng.release_arrivals()
 
 
 @pytest.mark.parametrize("edit", ["replace", "in_place"])
