@@ -739,6 +739,63 @@ int plato_agg_scaled_sum(const float* const* d_x_f32, const int64_t* const* d_x_
                          size_t n_f32, size_t n_i64, hipStream_t stream);
 
 /*
+ * Sub-model aggregation (examples/model_search/{heterofl,fjord,fedrolex,anycostfl}:
+ * Algorithm.aggregation): every client sends leading-corner boxes
+ * value[:s0, :s1, ...] of the global tensors, and every global element becomes the
+ * mean of the clients whose box covers it.
+ *
+ * plato_agg_submodel_mean  <- global[key][:s0, :s1, ...] += local[key] per client,
+ *                             count likewise, torch.div(global[key] - value, count)
+ *   for every element of every entry, with g its value in d_global:
+ *     acc = g; count = 0
+ *     for k = 0..K-1 in table order, if client k's box covers the element:
+ *       acc = acc + x_k (fp32, separately rounded); count = count + 1
+ *     out = (acc - g) / (float)max(count, 1)      (fp32 subtraction, IEEE division)
+ *   An element no client covers is (g - g) / 1: +0 for a finite g, NaN for an
+ *   infinite or NaN g.  g takes part in the rounding of every partial sum, and the
+ *   table order is the order of the sum, as in the reference.
+ *
+ *   An entry is a run of d_global / d_out seen as [P, Q, L] (row-major); client k's
+ *   box is (p <= P, q <= Q, l <= L) and covers the (i, j, t) with i < p, j < q,
+ *   t < l; its value is d_rows[k][src + (i * q + j) * l + t] (64-bit arithmetic).
+ *     a [D0] entry                [1, 1, D0]         box (1, 1, s0)
+ *     a [D0, D1, R...] entry      [D0, 1, D1 * R]    box (s0, 1, s1 * R)
+ *     a [D0, D1, D2] entry        [D0, D1, D2]       box (s0, s1, s2)
+ *   h_entries  n_entries rows of PLATO_AGG_SUBMODEL_ENTRY_WORDS int64:
+ *              {offset in d_global and d_out, P, Q, L, first tile, 0}, by ascending
+ *              offset and not overlapping; the first tile of an entry is the sum of
+ *              ceil(P * Q * L / PLATO_AGG_SUBMODEL_TILE) over the entries before it.
+ *              Elements of d_out that no entry holds are not written.
+ *   h_boxes    n_entries * K rows of PLATO_AGG_SUBMODEL_BOX_WORDS int64, entry-major:
+ *              {p, q, l, src}.  src == PLATO_AGG_SUBMODEL_ABSENT with zero extents:
+ *              the client has no box of this entry (an extent of 0 covers nothing
+ *              either).  A box in four dims would be a fifth and sixth word per row
+ *              under a new entry point; nothing reads them today.
+ *   h_row_len  K int64: the elements of each client row, for the bounds check
+ *   d_rows     device array of K row pointers (4-byte aligned rows)
+ *   d_tables   plato_agg_submodel_tables_bytes(K, n_entries) bytes (0: bad
+ *              arguments), 256-byte aligned: the call copies both tables there on
+ *              `stream` ahead of the kernel, so the host tables stay unchanged until
+ *              the stream has passed the call
+ *   d_out      n_out floats, 16-byte aligned
+ *   The three host tables are checked before any GPU work: extents and offsets in
+ *   range, no box above its entry's extents or past its client's row length.
+ *   1 <= K <= PLATO_AGG_SUBMODEL_MAX_K; at most 2^20 entries; fewer than 2^38
+ *   elements; n_entries == 0 or n_out == 0 is a success that launches nothing.
+ *   Bitwise repeatable; no atomics.
+ */
+#define PLATO_AGG_SUBMODEL_MAX_K 4096
+#define PLATO_AGG_SUBMODEL_MAX_ENTRIES 1048576
+#define PLATO_AGG_SUBMODEL_TILE 1024
+#define PLATO_AGG_SUBMODEL_ENTRY_WORDS 6
+#define PLATO_AGG_SUBMODEL_BOX_WORDS 4
+#define PLATO_AGG_SUBMODEL_ABSENT (-1)
+size_t plato_agg_submodel_tables_bytes(int K, size_t n_entries);
+int plato_agg_submodel_mean(const float* d_global, const float* const* d_rows, int K,
+                            const int64_t* h_row_len /* K */, const int64_t* h_entries, const int64_t* h_boxes,
+                            size_t n_entries, void* d_tables, float* d_out, size_t n_out, hipStream_t stream);
+
+/*
  * Single-process RCCL communicator over the GPUs one Plato server drives.
  * The reference has no collectives (aggregation runs on one CPU
  * process); these serve the multi-GPU engine behind the same

@@ -32,6 +32,11 @@ PLATO_AGG_ROBUST = {"median": 0, "nearest_mean": 1}
 PLATO_AGG_ROBUST_MAX_K = 256
 PLATO_AGG_PAIRDIST_CHAIN = 128
 PLATO_AGG_TRUST_TILE = 1024
+PLATO_AGG_SUBMODEL_MAX_K = 4096
+PLATO_AGG_SUBMODEL_TILE = 1024
+PLATO_AGG_SUBMODEL_ENTRY_WORDS = 6
+PLATO_AGG_SUBMODEL_BOX_WORDS = 4
+PLATO_AGG_SUBMODEL_ABSENT = -1
 
 _c_void_p = ctypes.c_void_p
 _c_size_t = ctypes.c_size_t
@@ -178,6 +183,10 @@ SIGNATURES = {
                  _c_void_p, _c_void_p]),
     "plato_agg_scaled_sum": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_size_t,
+                 _c_size_t, _c_void_p]),
+    "plato_agg_submodel_tables_bytes": (_c_size_t, [_c_int, _c_size_t]),
+    "plato_agg_submodel_mean": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,
                  _c_size_t, _c_void_p]),
     "plato_agg_comm_create": (_c_int, [_c_int, _c_void_p, ctypes.POINTER(_c_void_p)]),
     "plato_agg_comm_destroy": (_c_int, [_c_void_p]),

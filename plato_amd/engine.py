@@ -33,6 +33,7 @@ from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, s
 from .arrivals import Adopt, ArrivalTable, adopt_rule
 from .robust import RobustAggregates, RobustLaunches
 from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
+from .submodel import SubmodelAggregates
 
 
 def fp32_weights(values: Sequence[float]) -> np.ndarray:
@@ -156,9 +157,9 @@ class _Stager:
         stream.wait_stream(self.stream)
 
 
-class FedAvgEngine(RobustAggregates):
+class FedAvgEngine(RobustAggregates, SubmodelAggregates):
     """HIP FedAvg aggregation on one GPU (one process per GPU); the detector example's robust
-    aggregators are ``plato_amd.robust``'s."""
+    aggregators are ``plato_amd.robust``'s, the model-search examples' sub-model mean ``plato_amd.submodel``'s."""
 
     #: QSGD kernel variant (tuning / tests; None = the library default)
     qsgd_variant: int | None = None
@@ -184,6 +185,7 @@ class FedAvgEngine(RobustAggregates):
         self._arrivals = ArrivalTable()           # id(payload) -> Arrival; rows: its (fp32, int64) row pointers
         self._arrival_slabs: dict = {}
         self._arrival_base: DeviceArena | None = None  # the model arrivals are turned into deltas against
+        self._submodel = None                     # plato_amd.submodel's layouts, stagers and slab
 
     # ----------------------------------------------------------- allocation
     def _prepare(self, template: Mapping[str, torch.Tensor], k: int, codec: str = "native") -> ArenaLayout:

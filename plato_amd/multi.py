@@ -409,6 +409,12 @@ class MultiDeviceEngine:
     def aggregate_fltrust(self, payloads):
         raise NotImplementedError("robust aggregation (Fl-trust) runs on one GPU: use FedAvgEngine")
 
+    def begin_submodels(self, global_model, payloads, rule: str = "heterofl"):
+        raise NotImplementedError("sub-model aggregation runs on one GPU: use FedAvgEngine")
+
+    def aggregate_submodels(self, global_model, payloads, rule: str = "heterofl"):
+        raise NotImplementedError("sub-model aggregation runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""
