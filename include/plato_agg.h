@@ -769,8 +769,8 @@ int plato_agg_scaled_sum(const float* const* d_x_f32, const int64_t* const* d_x_
  *   h_boxes    n_entries * K rows of PLATO_AGG_SUBMODEL_BOX_WORDS int64, entry-major:
  *              {p, q, l, src}.  src == PLATO_AGG_SUBMODEL_ABSENT with zero extents:
  *              the client has no box of this entry (an extent of 0 covers nothing
- *              either).  A box in four dims would be a fifth and sixth word per row
- *              under a new entry point; nothing reads them today.
+ *              either).  Boxes in four dims, with keys that a client lacks, are
+ *              plato_agg_elastic_mean's below, under tables of its own.
  *   h_row_len  K int64: the elements of each client row, for the bounds check
  *   d_rows     device array of K row pointers (4-byte aligned rows)
  *   d_tables   plato_agg_submodel_tables_bytes(K, n_entries) bytes (0: bad
@@ -794,6 +794,80 @@ size_t plato_agg_submodel_tables_bytes(int K, size_t n_entries);
 int plato_agg_submodel_mean(const float* d_global, const float* const* d_rows, int K,
                             const int64_t* h_row_len /* K */, const int64_t* h_entries, const int64_t* h_boxes,
                             size_t n_entries, void* d_tables, float* d_out, size_t n_out, hipStream_t stream);
+
+/*
+ * Elastic sub-model aggregation (examples/model_search/sysheterofl: Algorithm.aggregation,
+ * sysheterofl_algorithm.py:134-181): the clients differ in depth, so a client lacks
+ * whole keys of the global model, and in width per stage; a 4-D tensor is boxed on
+ * all four dims, and every key takes part, running statistics included.
+ *
+ * The rule, with G = algorithm.model.state_dict() and the clients in arrival order;
+ * update_track is a bool (default true).  For every key of G, in G's order:
+ *   rank      by G[key].dim(): 4 -> 4, 2 -> 2, 1 -> 1, any other dim -> 0; with
+ *             update_track false a 1-D key whose name contains "running" or "tracked"
+ *             has rank 0.
+ *   a client  takes part in a key only if the key is in its payload and the rank is at
+ *             least 1.  Its tensor is float32, has as many dims as G[key] and no extent
+ *             above G[key]'s, and covers the leading-corner box [:s0, :s1, :s2, :s3]
+ *             ([:s0, :s1]; [:s0]).  An extent of 0 covers nothing.  Keys of the
+ *             payload that G lacks are ignored; keys of rank 0 are never read.
+ *   element   acc = g; acc = acc + x_k over the clients that hold the key and cover
+ *             the element, in arrival order; out = (acc - g) / max(count, 1): every
+ *             operation a separately rounded fp32 one, the division IEEE.  An element
+ *             nobody covers (a whole entry no client of the round holds included) is
+ *             (g - g) / 1: +0 for a finite g (also for -0), NaN for an infinite or
+ *             NaN g.
+ *   result    float32 for every key.  A key of G that is not float32 gives float32
+ *             zeros of its shape if its dtype is an integer one and its dim is not 1,
+ *             2 or 4 (the 0-D int64 num_batches_tracked counters: an int64 g - g is
+ *             exactly 0), written by the caller without GPU work; any other
+ *             non-float32 key of G is refused by the caller.
+ *
+ * plato_agg_elastic_mean computes the float32 keys.
+ *   An entry is a run of d_global / d_out seen row-major as [A, B, C, D]; a box
+ *   (a <= A, b <= B, c <= C, d <= D) covers the (i, j, t, u) with i < a, j < b, t < c,
+ *   u < d, and its value is d_rows[client][src + ((i * b + j) * c + t) * d + u]
+ *   (64-bit arithmetic).  Trailing dims in which every holder has the full extent
+ *   may be merged into the dim before them (a convolution whose holders all have
+ *   the global kernel size is [1, 1, D0, D1 * kh * kw], boxes (1, 1, s0, s1 * kh * kw));
+ *   the kernel pays an integer division only for view dims whose extent is not 1.
+ *   h_entries  n_entries rows of PLATO_AGG_ELASTIC_ENTRY_WORDS int64:
+ *              {offset in d_global and d_out, A, B, C, D, first tile, first box,
+ *              number of boxes}, by ascending offset and not overlapping.  The first
+ *              tile of an entry is the sum of ceil(A * B * C * D /
+ *              PLATO_AGG_ELASTIC_TILE) over the entries before it, its first box the
+ *              sum of their numbers of boxes; the box ranges tile [0, n_boxes).
+ *              Elements of d_out that no entry holds are not written.
+ *   h_boxes    n_boxes rows of PLATO_AGG_ELASTIC_BOX_WORDS int64: {a, b, c, d, src,
+ *              client}.  The table is compact: an entry lists the clients that hold
+ *              it and no others, by strictly ascending client (0 <= client < K), so
+ *              the arrival order is the order of the sum; an entry nobody holds has
+ *              zero boxes, and there is no absent encoding.
+ *   h_row_len  K int64: the elements of each client row (0 is legal: the client holds
+ *              no key), for the bounds check src + a * b * c * d <= h_row_len[client]
+ *   d_rows     device array of K row pointers (4-byte aligned rows)
+ *   d_tables   plato_agg_elastic_tables_bytes(n_entries, n_boxes) bytes (0: bad
+ *              arguments), 256-byte aligned: the call copies both tables there on
+ *              `stream` ahead of the kernel, so the host tables stay unchanged until
+ *              the stream has passed the call
+ *   d_out      n_out floats, 16-byte aligned
+ *   The three host tables are checked before any GPU work (negative status,
+ *   plato_agg_last_error): K, the entries' ranges, the tile column, the box ranges,
+ *   the clients' order, the extents, the row lengths.
+ *   1 <= K <= PLATO_AGG_ELASTIC_MAX_K; at most 2^20 entries and 2^20 * K boxes;
+ *   fewer than 2^38 elements; n_entries == 0 or n_out == 0 is a success that launches
+ *   nothing.  Nothing is sized by K.  Bitwise repeatable; no atomics.
+ */
+#define PLATO_AGG_ELASTIC_MAX_K 4096
+#define PLATO_AGG_ELASTIC_MAX_ENTRIES 1048576
+#define PLATO_AGG_ELASTIC_TILE 1024
+#define PLATO_AGG_ELASTIC_ENTRY_WORDS 8
+#define PLATO_AGG_ELASTIC_BOX_WORDS 6
+size_t plato_agg_elastic_tables_bytes(size_t n_entries, size_t n_boxes);
+int plato_agg_elastic_mean(const float* d_global, const float* const* d_rows, int K,
+                           const int64_t* h_row_len /* K */, const int64_t* h_entries, size_t n_entries,
+                           const int64_t* h_boxes, size_t n_boxes, void* d_tables,
+                           float* d_out, size_t n_out, hipStream_t stream);
 
 /*
  * Single-process RCCL communicator over the GPUs one Plato server drives.

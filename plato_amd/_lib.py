@@ -37,6 +37,10 @@ PLATO_AGG_SUBMODEL_TILE = 1024
 PLATO_AGG_SUBMODEL_ENTRY_WORDS = 6
 PLATO_AGG_SUBMODEL_BOX_WORDS = 4
 PLATO_AGG_SUBMODEL_ABSENT = -1
+PLATO_AGG_ELASTIC_MAX_K = 4096
+PLATO_AGG_ELASTIC_TILE = 1024
+PLATO_AGG_ELASTIC_ENTRY_WORDS = 8
+PLATO_AGG_ELASTIC_BOX_WORDS = 6
 
 _c_void_p = ctypes.c_void_p
 _c_size_t = ctypes.c_size_t
@@ -188,6 +192,10 @@ SIGNATURES = {
     "plato_agg_submodel_mean": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,
                  _c_size_t, _c_void_p]),
+    "plato_agg_elastic_tables_bytes": (_c_size_t, [_c_size_t, _c_size_t]),
+    "plato_agg_elastic_mean": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p,
+                 _c_void_p, _c_size_t, _c_void_p]),
     "plato_agg_comm_create": (_c_int, [_c_int, _c_void_p, ctypes.POINTER(_c_void_p)]),
     "plato_agg_comm_destroy": (_c_int, [_c_void_p]),
     "plato_agg_comm_size": (_c_int, [_c_void_p]),

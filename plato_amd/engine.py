@@ -31,6 +31,7 @@ import torch
 from . import _lib
 from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, same_f32_bits
 from .arrivals import Adopt, ArrivalTable, adopt_rule
+from .elastic import ElasticAggregates
 from .robust import RobustAggregates, RobustLaunches
 from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
 from .submodel import SubmodelAggregates
@@ -157,9 +158,10 @@ class _Stager:
         stream.wait_stream(self.stream)
 
 
-class FedAvgEngine(RobustAggregates, SubmodelAggregates):
+class FedAvgEngine(RobustAggregates, SubmodelAggregates, ElasticAggregates):
     """HIP FedAvg aggregation on one GPU (one process per GPU); the detector example's robust
-    aggregators are ``plato_amd.robust``'s, the model-search examples' sub-model mean ``plato_amd.submodel``'s."""
+    aggregators are ``plato_amd.robust``'s, the model-search examples' sub-model means ``plato_amd.submodel``'s and
+    ``plato_amd.elastic``'s."""
 
     #: QSGD kernel variant (tuning / tests; None = the library default)
     qsgd_variant: int | None = None
@@ -186,6 +188,7 @@ class FedAvgEngine(RobustAggregates, SubmodelAggregates):
         self._arrival_slabs: dict = {}
         self._arrival_base: DeviceArena | None = None  # the model arrivals are turned into deltas against
         self._submodel = None                     # plato_amd.submodel's layouts, stagers and slab
+        self._elastic = None                      # plato_amd.elastic's
 
     # ----------------------------------------------------------- allocation
     def _prepare(self, template: Mapping[str, torch.Tensor], k: int, codec: str = "native") -> ArenaLayout:

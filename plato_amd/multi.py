@@ -415,6 +415,12 @@ class MultiDeviceEngine:
     def aggregate_submodels(self, global_model, payloads, rule: str = "heterofl"):
         raise NotImplementedError("sub-model aggregation runs on one GPU: use FedAvgEngine")
 
+    def begin_elastic(self, global_model, payloads, update_track: bool = True):
+        raise NotImplementedError("elastic aggregation runs on one GPU: use FedAvgEngine")
+
+    def aggregate_elastic(self, global_model, payloads, update_track: bool = True):
+        raise NotImplementedError("elastic aggregation runs on one GPU: use FedAvgEngine")
+
 
 class MultiRound:
     """One bucket-sharded aggregation: stage (any order), launch on every GPU, assemble."""

@@ -3,4 +3,5 @@
 from .fedavg import DeltasAggregationMixin, FusedAggregationMixin, make_server  # noqa: F401
 from .ingest import WireIngestMixin  # noqa: F401
 from .robust import DetectorAggregationMixin, RobustAggregationMixin, TrustAggregationMixin  # noqa: F401
+from .elastic import ElasticAggregationMixin  # noqa: F401
 from .submodel import SubmodelAggregationMixin  # noqa: F401

@@ -9,7 +9,8 @@ with its channel sorting and sBN, ``clients_processed``) are the base class's, u
     Server = make_server(base=heterofl_server.Server, mixin=SubmodelAggregationMixin)
 
 HeteroFL and FjORD take ``submodel_rule = "heterofl"`` (the default), FedRolex and AnyCostFL
-``"fedrolex"`` (a 3-D entry is boxed on its three dims).  ``sysheterofl`` is another rule and is not built.
+``"fedrolex"`` (a 3-D entry is boxed on its three dims).  ``sysheterofl`` is another rule, under names of its own:
+``plato_amd.servers.elastic``.
 """
 
 from __future__ import annotations

@@ -14,9 +14,9 @@ the global ``state_dict`` and the clients' in arrival order, for every key of G 
   entry and its clients' values are never read either.
 
 The tables of :func:`build_tables` are pure numpy; :class:`SubmodelRound` stages and launches.  Out of
-scope: ``sysheterofl`` (boxes on four dims, keys missing per client, int64 counters divided as floats; the
-box table's absent encoding and the header's note on a fourth extent leave room for it), several GPUs,
-bf16 and QSGD payloads, and rows prestaged at arrival (sub-model payloads are staged here).
+scope: ``sysheterofl`` (boxes on four dims, keys missing per client, int64 counters divided as floats: it
+is ``plato_amd.elastic``, with an entry point and tables of its own), several GPUs, bf16 and QSGD
+payloads, and rows prestaged at arrival (sub-model payloads are staged here).
 """
 
 from __future__ import annotations
