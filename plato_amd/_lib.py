@@ -188,6 +188,10 @@ SIGNATURES = {
     "plato_agg_scaled_sum": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_float, _c_void_p, _c_void_p, _c_size_t,
                  _c_size_t, _c_void_p]),
+    "plato_agg_column_std": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
+    "plato_agg_add_scaled_rows": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_float, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
     "plato_agg_submodel_tables_bytes": (_c_size_t, [_c_int, _c_size_t]),
     "plato_agg_submodel_mean": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,

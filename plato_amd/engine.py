@@ -33,7 +33,7 @@ from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, s
 from .arrivals import Adopt, ArrivalTable, adopt_rule
 from .elastic import ElasticAggregates
 from .robust import RobustAggregates, RobustLaunches
-from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
+from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key, payload_fingerprint
 from .submodel import SubmodelAggregates
 
 
@@ -369,6 +369,14 @@ class FedAvgEngine(RobustAggregates, SubmodelAggregates, ElasticAggregates):
         A copy still in flight into the row is ordered before any later copy into it (one copy stream)."""
         self._arrivals.drop(payload)
 
+    def refresh_arrival(self, payload) -> None:
+        """``payload``'s staged row was changed on the device and the payload written to match it (the
+        attack simulation's write-back): its record follows the payload's new version counters, so the
+        next round still adopts the row."""
+        rec = self._arrivals.get(id(payload))
+        if rec is not None and rec.payload is payload:
+            rec.fingerprint = payload_fingerprint(payload)
+
     def release_arrivals(self) -> None:
         """Return every arrival slot (after the round that used them has completed, or failed)."""
         self._arrivals.release()
@@ -615,6 +623,7 @@ class AggregationRound(RobustLaunches):
         # per slot: device pointers of its fp32 / int64 rows (round slab or an arrival slot)
         self._pf = [0] * capacity
         self._pi = [0] * capacity
+        self._rows: list = [None] * capacity  # per slot: (slab, row) that holds it (fetch_rows)
         # QSGD codec: per slot max_v per entry (layout order) and the clients' quantization level
         self._mv: list = [None] * capacity
         self._level: int | None = None
@@ -688,6 +697,7 @@ class AggregationRound(RobustLaunches):
         self.stager.put(payload, self.slab.f32[slot], self.slab.i64[slot])
         pf, pi = self.slab.row_pointers([slot])
         self._pf[slot], self._pi[slot] = int(pf[0]), int(pi[0])
+        self._rows[slot] = (self.slab, slot)
         self._converted.discard((self._pf[slot], self._pi[slot]))  # fresh weights in the row
         if self.deltas:
             self._to_delta(slot)  # behind this client's H2D on the copy stream
@@ -716,6 +726,7 @@ class AggregationRound(RobustLaunches):
             return False  # a delta against another model (or a weight round): stage the payload again
         self._coded_scales(slot, payload)
         self._pf[slot], self._pi[slot] = rec.rows
+        self._rows[slot] = rec.slot
         if how is Adopt.AS_FORMED:
             self._converted.add(rec.rows)  # turned into its delta at arrival, against this round's baseline
         elif self.deltas:  # the arrival row holds the weights: its delta now, in place (the row is this round's)
@@ -1466,9 +1477,11 @@ class _DecodedRound(AggregationRound):
         self.staged = [False] * parent.capacity
         self._pf = [0] * parent.capacity
         self._pi = [0] * parent.capacity
+        self._rows = [None] * parent.capacity
         rows = self.slab.row_pointers(range(len(slots)))
         for r, slot in enumerate(slots):
             self._pf[slot], self._pi[slot] = int(rows[0][r]), int(rows[1][r])
+            self._rows[slot] = (self.slab, r)
             self.staged[slot] = True
         self._mv = [None] * parent.capacity
         self._level = None

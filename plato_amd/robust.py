@@ -3,6 +3,8 @@ Multi-krum, Bulyan and Fl-trust.  All have one shape: K native payloads staged a
 pointer tables of the rows, one to three kernels with at most one blocking read for a decision taken on the
 host (``plato_amd.krum``, ``plato_amd.trust``), an all-float32 result.  :class:`RobustLaunches` is that shape
 as a mixin of ``engine.AggregationRound``, :class:`RobustAggregates` the one-call forms of ``FedAvgEngine``.
+``launch_attack`` is the attack simulation that the example runs before them (examples/detector/attacks.py):
+it poisons the attackers' staged rows in place, and the aggregators then read those rows.
 """
 
 from __future__ import annotations
@@ -200,12 +202,8 @@ class RobustLaunches:
             self._k = 3 * k  # the rows are read by the mean, the statistics and the sum
             mean_f, mean_i = self._out_rows()
             self._mean_rows(tf, ti, k, mean_f, mean_i, stream)
-            nbytes = _lib.lib().plato_agg_trust_stats_workspace(k, lay.n_f32, lay.n_i64)
-            work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-            stats = torch.empty(3 * k + 1, dtype=torch.float64, device=dev)
             with self._timed("trust_stats", stream):
-                _lib.call("plato_agg_trust_stats", *self._regions(tf, ti), k, *self._regions(mean_f, mean_i), EPS,
-                          lay.n_f32, lay.n_i64, work.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+                stats, work = self._trust_stats(tf, ti, k, mean_f, mean_i, lay.n_f32, lay.n_i64, stream, EPS)
             host_stats = stats.cpu().numpy()  # stream-ordered, blocking: the scalars are formed on the host
             t0 = time.perf_counter()
             self.trust = self.engine.last_trust = fltrust_weights(host_stats, k, EPS)
@@ -218,6 +216,130 @@ class RobustLaunches:
             return out_f, out_i, (mean_f, mean_i, work, stats, scal)
 
         self._launch_rows("launch_fltrust", order, body)
+
+    def _trust_stats(self, tf, ti, k: int, ref_f, ref_i, n_f32: int, n_i64: int, stream, eps: float = 0.0):
+        """([3k + 1] float64 on the device, the workspace to keep until they are read):
+        ``plato_agg_trust_stats`` of k rows against a vector."""
+        dev = self.engine.device
+        nbytes = _lib.lib().plato_agg_trust_stats_workspace(k, n_f32, n_i64)
+        work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        stats = torch.zeros(3 * k + 1, dtype=torch.float64, device=dev)  # nothing is written for no coordinates
+        _lib.call("plato_agg_trust_stats", tf.data_ptr() if n_f32 else None, ti.data_ptr() if n_i64 else None, k,
+                  ref_f.data_ptr() if n_f32 else None, ref_i.data_ptr() if n_i64 else None, eps, n_f32, n_i64,
+                  work.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+        return stats, work
+
+    def launch_attack(self, kind: str, attackers: Sequence[int], *, per_round: int | None = None,
+                      lambada_value: float | None = None) -> None:
+        """The attack simulation of the reference's detector example (examples/detector/attacks.py) over
+        the staged rows of the attackers, given as slots in ``self.updates`` order: their weight rows are
+        poisoned in place, every other row stays as it is.
+
+        ``kind`` is ``"lie"`` (``per_round`` = ``clients.per_round``), ``"lambda"`` (``lambada_value`` =
+        ``clients.lambada_value``), ``"minmax"`` or ``"minsum"`` (``plato_amd.attacks.KINDS``).  The round
+        holds weights and its baseline: the attackers' deltas x - b are formed in scratch rows
+        (``plato_agg_compute_deltas``), the vector of the attack over them (``plato_agg_column_std``,
+        ``plato_agg_mean_rows``; the unit vector of Min-Max and Min-Sum by ``plato_agg_scale_by_norm``, their
+        lambda on the host from ``plato_agg_pairwise_sqdist`` and ``plato_agg_trust_stats``), and
+        ``plato_agg_add_scaled_rows`` adds it to the weight rows.  LIE with one attacker changes nothing, as
+        in the reference.  ``self.attack`` holds the scalars and the vector's two device regions
+        (``"vector"``).  Runs on the round's one device; the launches that follow (``launch_robust`` and the
+        others) read the poisoned rows."""
+        from . import attacks
+
+        if kind not in attacks.KINDS.values():
+            raise ValueError(f"unknown attack {kind!r} (supported: {sorted(attacks.KINDS.values())})")
+        if kind == "lie" and per_round is None:
+            raise ValueError("the LIE attack needs per_round (clients.per_round)")
+        if kind == "lambda" and lambada_value is None:
+            raise ValueError("the Lambda attack needs lambada_value (clients.lambada_value)")
+        if not self.has_baseline:
+            raise ValueError("launch_attack forms the attackers' deltas: stage the baseline first")
+        slots, tf, ti, stream = self._robust_rows("launch_attack", attackers)
+        lay, dev, a = self.layout, self.engine.device, len(slots)
+        self.attack = self.engine.last_attack = {"kind": kind, "attackers": slots, "poisoned": False}
+        if kind == "lie" and a == 1:  # "LIE attack does not apply to solo attacker"
+            return
+        n_f, n_i, h = lay.n_f32, lay.n_i64, stream.cuda_stream
+        base = self._base
+        df = torch.empty((a, lay.row_f32), dtype=torch.float32, device=dev)
+        di = torch.empty((a, lay.row_i64), dtype=torch.int64, device=dev)
+        with self._timed("attack_deltas", stream):
+            for j, slot in enumerate(slots):
+                _lib.call("plato_agg_compute_deltas", self._pf[slot], self._pi[slot] if n_i else None,
+                          base.f32.data_ptr(), base.i64.data_ptr() if n_i else None, df[j].data_ptr(),
+                          di[j].data_ptr() if n_i else None, n_f, n_i, h)
+        dtf, dti = self.engine._pointer_tables(
+            np.asarray([df[j].data_ptr() for j in range(a)], dtype=np.int64),
+            np.asarray([di[j].data_ptr() for j in range(a)], dtype=np.int64))
+        v_f, v_i = self._out_rows()
+        info = self.attack
+        if kind == "lie":
+            with self._timed("column_std", stream):
+                _lib.call("plato_agg_column_std", *self._regions(dtf, dti), a, *self._regions(v_f, v_i),
+                          *self._sizes(stream))
+            info["z"] = attacks.lie_z(per_round, a)
+            s = -np.float32(info["z"])
+        elif kind == "lambda":
+            self._mean_rows(dtf, dti, a, v_f, v_i, stream)
+            s = -np.float32(lambada_value)
+        else:
+            minsum = kind == "minsum"
+            avg_f, avg_i = self._out_rows()
+            self._mean_rows(*((tf, ti) if minsum else (dtf, dti)), a, avg_f, avg_i, stream)  # Min-Sum: of the weights
+            with self._timed("attack_stats", stream):
+                s_avg, w0 = self._trust_stats(dtf, dti, a, avg_f, avg_i, n_f, n_i, stream)
+            h_avg = s_avg.cpu().numpy()  # stream-ordered, blocking: the norm is rounded on the host
+            with np.errstate(invalid="ignore"):
+                norm = np.float32(np.sqrt(h_avg[3 * a]))  # float64 root, rounded to fp32 once
+            d_norm = torch.from_numpy(np.asarray([norm], dtype=np.float32)).to(dev)
+            with self._timed("attack_unit", stream):
+                _lib.call("plato_agg_scale_by_norm", avg_f.data_ptr(), n_f, d_norm.data_ptr(), 0.0, v_f.data_ptr(), h)
+                if n_i:
+                    _lib.call("plato_agg_scale_by_norm", avg_i.data_ptr(), n_i, d_norm.data_ptr(), 0.0,
+                              v_i.data_ptr(), h)
+            # avg against p: avg's two regions are fp32, each a one-row table of an fp32 region
+            atab = torch.tensor([avg_f.data_ptr(), avg_i.data_ptr()], dtype=torch.int64, device=dev)
+            with self._timed("attack_stats_unit", stream):
+                s_p, w1 = self._trust_stats(dtf, dti, a, v_f, v_i, n_f, n_i, stream)
+                s_af, w2 = self._trust_stats(atab[:1], None, 1, v_f, None, n_f, 0, stream)
+                s_ai, w3 = self._trust_stats(atab[1:], None, 1, v_i, None, n_i, 0, stream)
+            dist = self._pairwise_sqdist(a, dtf, dti, stream)  # blocking: the statistics above are done too
+            h_p, h_af, h_ai = s_p.cpu().numpy(), s_af.cpu().numpy(), s_ai.cpu().numpy()
+            t0 = time.perf_counter()
+            stats = attacks.SearchStats(uu=h_avg[a:2 * a], ua=h_avg[:a], up=h_p[:a], aa=float(h_avg[3 * a]),
+                                        pp=float(h_p[3 * a]), ap=float(h_af[0] + h_ai[0]))
+            lam = (attacks.min_sum_lambda if minsum else attacks.min_max_lambda)(stats, dist)
+            self.timings["attack_search_ms"] = (time.perf_counter() - t0) * 1e3
+            info.update(lam=lam, norm=norm, stats=stats,
+                        threshold=(attacks.min_sum_threshold if minsum else attacks.min_max_threshold)(dist))
+            # -1 * lambda_succ with the reference's integer 0 when nothing succeeded: +0, not -0
+            s = lam if minsum else (np.float32(0.0) if lam == 0 else -lam)
+            del w0, w1, w2, w3, atab
+        with self._timed("add_scaled_rows", stream):
+            _lib.call("plato_agg_add_scaled_rows", *self._regions(tf, ti), a, float(s), *self._regions(v_f, v_i),
+                      *self._sizes(stream))
+        info.update(s=np.float32(s), vector=(v_f[:n_f], v_i[:n_i]), poisoned=True)
+        self._attack_keep = (df, di, dtf, dti, tf, ti)  # until the stream has passed the launches
+
+    def fetch_rows(self, slots: Sequence[int]):
+        """[(fp32 region, int64 region)] of the staged rows ``slots`` as host tensors, stream-ordered
+        behind the launches so far (the poisoned rows after :meth:`launch_attack`).  Blocks."""
+        slots = self._check_slots(slots)
+        stream = torch.cuda.current_stream(self.engine.device)
+        self.stager.fence(stream)
+        lay = self.layout
+        out = []
+        for slot in slots:
+            row_f, row_i = self._row_tensors(slot)
+            out.append((row_f[: lay.n_f32].cpu(), row_i[: lay.n_i64].cpu()))
+        self._resolve_timers()
+        return out
+
+    def _row_tensors(self, slot: int):
+        """The device tensors of a staged slot's rows: in the round's slab, or an arrival slab."""
+        slab, row = self._rows[slot]
+        return slab.f32[row], slab.i64[row]
 
 
 class RobustAggregates:

@@ -13,9 +13,15 @@ every client by its clipped cosine with the mean model (``plato_agg_mean_rows``,
 ``plato_agg_trust_stats``, the scalars on the host in ``plato_amd.trust``, ``plato_agg_scaled_sum``); it is
 :class:`TrustAggregationMixin`'s, which again adds it to its parent's.  One ``aggregate_weights`` serves
 the three: a class differs in its table of names only.  The detector server's ``weights_received``
-pipeline (attack simulation, filters) is the base class's and runs before this hook, unchanged::
+pipeline runs before this hook; its filters are the base class's, unchanged, and its attack simulation
+(``weights_attacked``) runs on the GPU with :class:`AttackSimulationMixin` for the attacks "LIE",
+"Lambda_attack", "Min-Max" and "Min-Sum" (``plato_amd.attacks``)::
 
     Server = make_server(base=detector_server.Server, mixin=RobustAggregationMixin)
+
+    class Mixin(AttackSimulationMixin, DetectorAggregationMixin):
+        pass
+    Server = make_server(base=detector_server.Server, mixin=Mixin)
 """
 
 from __future__ import annotations
@@ -23,7 +29,7 @@ from __future__ import annotations
 from .. import tracing
 from ..arena import payload_codec
 from ..arrivals import adopt_or_put
-from .fedavg import FusedAggregationMixin
+from .fedavg import FusedAggregationMixin, _EngineHolder
 
 
 def _secure_aggregation_type():
@@ -135,3 +141,88 @@ class TrustAggregationMixin(DetectorAggregationMixin):
     ("Krum" and "Afa" have no behaviour to match: INTEGRATION.md §12)."""
 
     aggregators = {**DetectorAggregationMixin.aggregators, "Fl-trust": _fl_trust}
+
+
+def _clients_config(name: str):
+    """``Config().clients.<name>``, or None where it is not set or Plato is not installed.  A
+    configuration that fails to load raises: the round must not fall to the host path in silence."""
+    try:
+        from plato.config import Config
+    except ImportError:
+        return None
+    return getattr(Config().clients, name, None)
+
+
+class AttackSimulationMixin(_EngineHolder):
+    """``weights_attacked`` of the detector server (detector_server.py:81-112) on the GPU, for the
+    attacks ``attacks.get()`` can call with its four arguments and that draw nothing on the host: "LIE",
+    "Lambda_attack", "Min-Max" and "Min-Sum".  Every other ``clients.attack_type`` ("Gassian_attack",
+    "Fang", the "Oblivion-*" ones) and no attack at all go to the base class.
+
+    The attackers' payloads are staged as arrival rows (or adopted, where they were staged at arrival),
+    poisoned there in place (``AggregationRound.launch_attack``) and, by default, copied back into the
+    payload tensors, which the reference mutates in place and its filters and callbacks read.  The
+    aggregation hook that follows adopts the poisoned rows: nothing is staged twice.  Composes with the
+    aggregation mixins by inheritance; on several ``aggregation_devices`` the attack runs on the first
+    and always writes back.
+    """
+
+    #: None = ``Config().clients.attack_type`` / ``.per_round`` / ``.lambada_value``
+    attack_simulation_type = None
+    attack_per_round = None
+    attack_lambada_value = None
+    #: copy the poisoned rows back into the attackers' payload tensors (D2H); False for rounds whose
+    #: payloads nothing reads between the attack and the aggregation on the device
+    attack_writeback = True
+
+    def _attack_setting(self, own: str, name: str):
+        value = getattr(self, own)
+        return value if value is not None else _clients_config(name)
+
+    def weights_attacked(self, weights_received):
+        from ..attacks import KINDS
+
+        kind = KINDS.get(self._attack_setting("attack_simulation_type", "attack_type"))
+        if kind is None:
+            return super().weights_attacked(weights_received)
+        at = [i for i, update in enumerate(self.updates) if update.client_id in self.attacker_list]
+        if not at or (kind == "lie" and len(at) == 1):  # no attacker; "LIE attack does not apply to solo attacker"
+            return weights_received
+        payloads = [weights_received[i] for i in at]
+        codec = payload_codec(payloads[0])
+        if codec != "native":
+            raise ValueError(f"the attack simulation takes native payloads, not {codec} codes")
+        params = {}
+        if kind == "lie":
+            params["per_round"] = self._attack_setting("attack_per_round", "per_round")
+        elif kind == "lambda":
+            params["lambada_value"] = self._attack_setting("attack_lambada_value", "lambada_value")
+        engine = self.aggregation_engine()
+        multi = getattr(engine, "primary", None) is not None
+        if multi:
+            engine = engine.primary
+        baseline = self.algorithm.extract_weights()
+        rnd = engine.begin(baseline, len(payloads))
+        rnd.deltas = False  # the rows stay weights: the deltas are formed in scratch
+        rnd.put_baseline(baseline)
+        in_arrival_rows = True
+        with tracing.range("plato_amd.attack.stage"):
+            for slot, payload in enumerate(payloads):
+                if rnd.adopt(slot, payload):
+                    continue
+                engine.drop_arrival(payload)  # staged as a delta, or written since: stage it again
+                if engine.prestage(payload, rnd.layout) and rnd.adopt(slot, payload):
+                    continue
+                rnd.put_client(slot, payload)
+                in_arrival_rows = False
+        with tracing.range("plato_amd.attack.launch"):
+            rnd.launch_attack(kind, range(len(payloads)), **params)
+        if self.attack_writeback or multi or not in_arrival_rows:
+            with tracing.range("plato_amd.attack.writeback"):
+                rows = rnd.fetch_rows(range(len(payloads)))
+                for payload, (row_f, row_i) in zip(payloads, rows):
+                    for name, src in rnd.layout.unpack(row_f, row_i).items():
+                        payload[name].copy_(src)  # in place, as perform_model_poisoning
+                    engine.refresh_arrival(payload)
+        self._plato_amd_attack = dict(rnd.attack, timings=dict(rnd.timings))
+        return weights_received

@@ -1,6 +1,7 @@
 """The robust aggregators' pieces at K x ResNet-18, HIP events, interleaved in one process.
 
     python scripts/bench_robust.py --algo krum|bulyan|fltrust [--ks 128,256] [--reps 10] [--host-ks 16,32]
+    python scripts/bench_robust.py --algo lie|minmax|minsum [--ks 20,32] [--reps 10] [--host-ks 4,8]
 
 Per K the algorithm's kernels and the fused FedAvg kernel on the same rows (the streaming yardstick) run in
 turn in every repetition; median and minimum over the repetitions.
@@ -23,6 +24,15 @@ row besides: the result written, or the mean read), its ratio to mean_rows, and 
 torch.cat and their torch.sum) from the flattened matrix on (flatten_weights, quadratic in copies, is not
 timed).
 
+lie, minmax, minsum (K is the number of attackers A): the attackers' delta rows are formed
+once (plato_agg_compute_deltas, timed apart).  lie: plato_agg_column_std beside plato_agg_mean_rows over the
+same delta rows (the two stream the same bytes) and plato_agg_add_scaled_rows into the weight rows; GB/s of
+each and column_std's ratio to mean_rows and to the HBM read rate.  minmax / minsum: the kernels of the
+search attacks (mean_rows, trust_stats against the average and against the unit vector, scale_by_norm,
+pairwise_sqdist, add_scaled_rows) and the host search (plato_amd.attacks) on the device's statistics.
+--host-ks: the attack's op sequence after flatten_weights (attacks.py:186-199 for lie; :247-287 and
+:379-419 for the searches: the A x A distance loop and the search's passes of `torch.norm(X - v, dim=1) ** 2`).
+
 --host-ks runs the reference's own op sequence on this host's CPU at 16 threads, on the same synthetic rows.
 """
 
@@ -40,7 +50,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from plato_amd import _lib, workloads  # noqa: E402
+from plato_amd import _lib, attacks, workloads  # noqa: E402
 from plato_amd.arena import ArenaLayout  # noqa: E402
 from plato_amd.engine import ClientSlab, DeviceArena, FedAvgEngine, fedavg_weights, fp32_weights  # noqa: E402
 from plato_amd.krum import bulyan_select, multi_krum_select  # noqa: E402
@@ -202,6 +212,124 @@ def fltrust_device(b):
     return {"mean_rows": mean, "trust_stats": trust_stats, "scaled_sum": scaled_sum}, report
 
 
+def attack_device(kind):
+    def device(b):
+        a, n_f, n_i, lay = b.k, b.n_f, b.n_i, b.layout
+        df = torch.empty((a, lay.row_f32), dtype=torch.float32, device=b.dev)
+        di = torch.empty((a, lay.row_i64), dtype=torch.int64, device=b.dev)
+        dtf = torch.tensor([df[j].data_ptr() for j in range(a)], dtype=torch.int64, device=b.dev)
+        dti = torch.tensor([di[j].data_ptr() for j in range(a)], dtype=torch.int64, device=b.dev)
+        row = lambda: (torch.empty(lay.row_f32, dtype=torch.float32, device=b.dev),  # noqa: E731
+                       torch.empty(lay.row_i64, dtype=torch.float32, device=b.dev))
+        (avg_f, avg_i), (v_f, v_i) = row(), row()
+        pf, pi = b.slab.row_pointers(range(a))
+
+        def deltas():
+            for j in range(a):
+                _lib.call("plato_agg_compute_deltas", int(pf[j]), int(pi[j]), b.base.f32.data_ptr(), b.base.i64.data_ptr(),
+                          df[j].data_ptr(), di[j].data_ptr(), n_f, n_i, b.sh)
+
+        def mean(tf=dtf, ti=dti):
+            _lib.call("plato_agg_mean_rows", tf.data_ptr(), ti.data_ptr(), a, avg_f.data_ptr(), avg_i.data_ptr(), n_f, n_i, b.sh)
+
+        def std():
+            _lib.call("plato_agg_column_std", dtf.data_ptr(), dti.data_ptr(), a, v_f.data_ptr(), v_i.data_ptr(), n_f, n_i, b.sh)
+
+        def add(s):
+            return lambda: _lib.call("plato_agg_add_scaled_rows", b.tf.data_ptr(), b.ti.data_ptr(), a, s, v_f.data_ptr(),
+                                     v_i.data_ptr(), n_f, n_i, b.sh)
+
+        deltas()
+        outputs(b)
+        row_bytes = n_f * 4 + n_i * 8
+        d = n_f + n_i
+
+        def lines(times, gb_of):
+            med = {name: statistics.median(ms) for name, ms in times.items()}
+            for name, ms in times.items():
+                line = f"  {name:18s} median {med[name]:9.3f} ms   min {min(ms):9.3f} ms   max {max(ms):9.3f} ms"
+                if name in gb_of:
+                    line += f"   {gb_of[name] / med[name] * 1e3:8.1f} GB/s   {med[name] / med['mean_rows']:.2f} x mean_rows"
+                print(line)
+            return med
+
+        if kind == "lie":
+            s = -float(np.float32(attacks.lie_z(100, a)))
+
+            def report(times):
+                read = (a * row_bytes + d * 4) / 1e9  # A rows read, one fp32 row written
+                print(f"A={a} D={d} reps={b.reps} HBM floor of one read pass {a * row_bytes / HBM_BYTES_PER_S * 1e3:.3f} ms")
+                med = lines(times, {"mean_rows": read, "column_std": read, "fedavg": read + row_bytes / 1e9,
+                                    "add_scaled_rows": (2 * a * row_bytes + d * 4) / 1e9,
+                                    "compute_deltas": 3 * a * row_bytes / 1e9})
+                print(f"  column_std reads at {read / med['column_std'] * 1e3 / (HBM_BYTES_PER_S / 1e9):.1%} of the HBM read rate; "
+                      f"LIE kernels (compute_deltas + column_std + add_scaled_rows) "
+                      f"{med['compute_deltas'] + med['column_std'] + med['add_scaled_rows']:.3f} ms")
+
+            return {"mean_rows": mean, "column_std": std, "add_scaled_rows": add(s), "compute_deltas": deltas}, report
+
+        minsum = kind == "minsum"
+        stats_work = torch.empty(_lib.lib().plato_agg_trust_stats_workspace(a, n_f, n_i), dtype=torch.uint8, device=b.dev)
+        s_avg = torch.zeros(3 * a + 1, dtype=torch.float64, device=b.dev)
+        s_p = torch.zeros(3 * a + 1, dtype=torch.float64, device=b.dev)
+        s_ap = torch.zeros(8, dtype=torch.float64, device=b.dev)
+        atab = torch.tensor([avg_f.data_ptr(), avg_i.data_ptr()], dtype=torch.int64, device=b.dev)
+        d_norm = torch.zeros(1, dtype=torch.float32, device=b.dev)
+        dist_work = torch.empty(_lib.lib().plato_agg_pairwise_sqdist_workspace(a, n_f, n_i), dtype=torch.uint8, device=b.dev)
+        dist = torch.empty((a, a), dtype=torch.float64, device=b.dev)
+        the_mean = (lambda: mean(b.tf, b.ti)) if minsum else mean  # Min-Sum: the mean of the weights
+
+        def stats(ref_f, ref_i, out):
+            return lambda: _lib.call("plato_agg_trust_stats", dtf.data_ptr(), dti.data_ptr(), a, ref_f.data_ptr(),
+                                     ref_i.data_ptr(), 0.0, n_f, n_i, stats_work.data_ptr(), out.data_ptr(), b.sh)
+
+        def unit():
+            _lib.call("plato_agg_scale_by_norm", avg_f.data_ptr(), n_f, d_norm.data_ptr(), 0.0, v_f.data_ptr(), b.sh)
+            _lib.call("plato_agg_scale_by_norm", avg_i.data_ptr(), n_i, d_norm.data_ptr(), 0.0, v_i.data_ptr(), b.sh)
+
+        def avg_dot_unit():
+            _lib.call("plato_agg_trust_stats", atab.data_ptr(), None, 1, v_f.data_ptr(), None, 0.0, n_f, 0,
+                      stats_work.data_ptr(), s_ap.data_ptr(), b.sh)
+            _lib.call("plato_agg_trust_stats", atab.data_ptr() + 8, None, 1, v_i.data_ptr(), None, 0.0, n_i, 0,
+                      stats_work.data_ptr(), s_ap.data_ptr() + 32, b.sh)
+
+        def sqdist():
+            _lib.call("plato_agg_pairwise_sqdist", dtf.data_ptr(), dti.data_ptr(), a, n_f, n_i, dist_work.data_ptr(),
+                      dist.data_ptr(), b.sh)
+
+        the_mean()
+        stats(avg_f, avg_i, s_avg)()
+        torch.cuda.synchronize()
+        h_avg = s_avg.cpu().numpy()
+        d_norm.copy_(torch.from_numpy(np.asarray([np.sqrt(h_avg[3 * a])], dtype=np.float32)))
+        unit()
+        stats(v_f, v_i, s_p)()
+        avg_dot_unit()
+        sqdist()
+        torch.cuda.synchronize()
+        h_p, h_ap, h_dist = s_p.cpu().numpy(), s_ap.cpu().numpy(), dist.cpu().numpy()
+        st = attacks.SearchStats(uu=h_avg[a:2 * a], ua=h_avg[:a], up=h_p[:a], aa=float(h_avg[3 * a]), pp=float(h_p[3 * a]),
+                                 ap=float(h_ap[0] + h_ap[4]))
+        search = attacks.min_sum_lambda if minsum else attacks.min_max_lambda
+        lam, search_ms = host_ms(lambda: search(st, h_dist))
+
+        def report(times):
+            read = (a * row_bytes + d * 4) / 1e9
+            print(f"A={a} D={d} reps={b.reps} lambda={float(lam)!r} HBM floor of one read pass "
+                  f"{a * row_bytes / HBM_BYTES_PER_S * 1e3:.3f} ms")
+            med = lines(times, {"mean_rows": read, "stats vs avg": read, "stats vs unit": read,
+                                "add_scaled_rows": (2 * a * row_bytes + d * 4) / 1e9, "compute_deltas": 3 * a * row_bytes / 1e9})
+            kernels = sum(v for name, v in med.items() if name != "fedavg")
+            print(f"  host search        median {statistics.median(search_ms):9.3f} ms   min {min(search_ms):9.3f} ms")
+            print(f"  {kind} kernels {kernels:.3f} ms + host search {statistics.median(search_ms):.3f} ms")
+
+        return {"mean_rows": the_mean, "stats vs avg": stats(avg_f, avg_i, s_avg), "unit vector": unit,
+                "stats vs unit": stats(v_f, v_i, s_p), "avg . unit": avg_dot_unit, "pairwise_sqdist": sqdist,
+                "add_scaled_rows": add(float(lam) if minsum else -float(lam)), "compute_deltas": deltas}, report
+
+    return device
+
+
 # ---------------------------------------------------------------------- per algorithm: the reference on the host
 def krum_host(x, k, n):
     """One selection step's distance loop of the reference."""
@@ -244,8 +372,42 @@ def fltrust_host(flattened_weights, k, n):
     yield "fl_trust after flatten_weights", ops
 
 
+def lie_host(x, k, n):
+    """lie_attack after flatten_weights: the mean it forms and does not use, the std, the product."""
+    def ops():
+        torch.mean(x, dim=0)
+        0.7549 * (-1 * torch.std(x, dim=0))
+
+    yield "mean, std, scale", ops
+
+
+def search_host(keep_failed):
+    """min_max_attack / min_sum_attack after flatten_weights: the A x A distance loop and the search, each
+    step one pass of `torch.norm(X - v, dim=1) ** 2`."""
+    def host(x, k, n):
+        def ops():
+            avg = torch.mean(x, 0)
+            p = avg / torch.norm(avg)
+            limit = torch.tensor([0.0])
+            for row in x:
+                dist = torch.norm((x - row), dim=1) ** 2
+                limit = torch.min(limit, torch.sum(dist)) if keep_failed else torch.max(limit, torch.max(dist))
+
+            def meets(lam):
+                dist = torch.norm((x - (avg - float(lam) * p)), dim=1) ** 2
+                return bool((torch.sum(dist) if keep_failed else torch.max(dist)) <= limit)
+
+            attacks.halving_search(meets, keep_failed)
+
+        yield "distance loop and search", ops
+
+    return host
+
+
 ALGOS = {"krum": (krum_device, krum_host), "bulyan": (bulyan_device, bulyan_host),
-         "fltrust": (fltrust_device, fltrust_host)}
+         "fltrust": (fltrust_device, fltrust_host), "lie": (attack_device("lie"), lie_host),
+         "minmax": (attack_device("minmax"), search_host(False)), "minsum": (attack_device("minsum"), search_host(True))}
+ATTACKS = ("lie", "minmax", "minsum")
 
 
 # ---------------------------------------------------------------------- shared
@@ -255,8 +417,8 @@ def device_part(algo, k: int, reps: int, layout, dev):
     fill_baseline(base, 23)
     fill_clients(slab, base, 23, k)
     stream = torch.cuda.current_stream(dev)
-    b = SimpleNamespace(k=k, reps=reps, dev=dev, layout=layout, slab=slab, n_f=layout.n_f32, n_i=layout.n_i64,
-                        sh=stream.cuda_stream)
+    b = SimpleNamespace(k=k, reps=reps, dev=dev, layout=layout, slab=slab, base=base, n_f=layout.n_f32,
+                        n_i=layout.n_i64, sh=stream.cuda_stream)
     b.tf, b.ti = tables(b, range(k))
     kernels, report = algo(b)
 
@@ -303,10 +465,13 @@ def host_part(algo, k: int, layout):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", required=True, choices=sorted(ALGOS))
-    ap.add_argument("--ks", default="128,256")
+    ap.add_argument("--ks", default=None, help="default: 128,256 (the attacks: 20,32 attackers)")
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--host-ks", default="16,32")
+    ap.add_argument("--host-ks", default=None, help="default: 16,32 (the attacks: 4,8)")
     args = ap.parse_args()
+    attack = args.algo in ATTACKS
+    args.ks = args.ks if args.ks is not None else ("20,32" if attack else "128,256")
+    args.host_ks = args.host_ks if args.host_ks is not None else ("4,8" if attack else "16,32")
     on_device, on_host = ALGOS[args.algo]
     layout = ArenaLayout.from_shapes(workloads.resnet(18, 10))
     if args.ks:
