@@ -50,6 +50,29 @@ def stats(cols: np.ndarray, ref: np.ndarray, eps=EPS32, exact: bool = True):
     return out, mag
 
 
+def exact_stats(x_f32: np.ndarray, x_i64: np.ndarray, ref: np.ndarray, eps):
+    """(sums, largest sum of |terms|) of plato_agg_trust_stats on rows, a reference vector and an eps that
+    all hold small integers: the 3K + 1 sums as Python ints, formed in int64 (the bound on the inputs, asserted,
+    keeps every sum below 2^62).  No partial sum of any order exceeds its row's sum of |terms|."""
+    assert x_f32.dtype == np.float32 and x_i64.dtype == np.int64 and ref.dtype == np.float32
+    n_f, k = x_f32.shape[1], x_f32.shape[0]
+    e = int(eps)
+    assert e == eps and ref.shape == (n_f + x_i64.shape[1],)
+    out, mag = [0] * (3 * k + 1), [0] * (3 * k + 1)
+    for x, r32 in ((x_f32, ref[:n_f]), (x_i64, ref[n_f:])):
+        c, r = x.astype(np.int64), r32.astype(np.int64)
+        assert np.array_equal(c.astype(np.float32), x) and np.array_equal(r.astype(np.float32), r32)  # fp32 holds them
+        top = max(int(np.abs(c).max(initial=0)) + abs(e), int(np.abs(r).max(initial=0)))
+        assert c.shape[1] * top * top < 2 ** 62
+        for i in range(k):
+            for at, terms in ((i, c[i] * r), (k + i, c[i] * c[i]), (2 * k + i, (c[i] + e) * (c[i] + e))):
+                out[at] += int(terms.sum())
+                mag[at] += int(np.abs(terms).sum())
+        out[3 * k] += int((r * r).sum())
+        mag[3 * k] += int((r * r).sum())
+    return out, max(mag)
+
+
 def scaled_sum(cols: np.ndarray, mul, div, post) -> np.ndarray:
     """plato_agg_scaled_sum: per coordinate the sequential fp32 sum over the rows of
     fp32(fp32(fp32(c * mul_k) / div_k) * post)."""

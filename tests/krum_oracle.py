@@ -37,6 +37,34 @@ def pairwise_sqdist(x_f32: np.ndarray, x_i64: np.ndarray) -> np.ndarray:
     return out
 
 
+def exact_sqdist(x_f32: np.ndarray, x_i64: np.ndarray, block: int = 1 << 18):
+    """(sums, largest sum, largest term) of the squared distances of rows that hold small integers: the
+    sums as [K][K] Python ints, exact.  They come from a float64 Gram product in column blocks,
+    |c_i - c_j|^2 = G_ii + G_jj - 2 G_ij: every product and every partial of a block is an integer below
+    block * max|c|^2 < 2^53 (asserted), so a block's G is exact in whatever order the product adds, and the
+    blocks are added as int64.  Every term of a distance is >= 0, so the largest partial sum that any order of
+    any pair can form is the largest sum; the largest term is bounded by (max c - min c)^2."""
+    assert x_f32.dtype == np.float32 and x_i64.dtype == np.int64 and x_f32.shape[0] == x_i64.shape[0]
+    k = x_f32.shape[0]
+    gram = np.zeros((k, k), dtype=np.int64)
+    lo, hi = 0, 0
+    for x in (x_f32, x_i64):
+        for at in range(0, x.shape[1], block):
+            c = x[:, at:at + block].astype(np.float64)
+            assert np.array_equal(c, np.rint(c)) and np.array_equal(c.astype(np.float32), c)  # integers that fp32 holds
+            top = float(np.abs(c).max())
+            assert c.shape[1] * top * top < 2.0 ** 53
+            g = c @ c.T
+            assert np.array_equal(g, np.rint(g))
+            gram += g.astype(np.int64)
+            lo, hi = min(lo, int(c.min())), max(hi, int(c.max()))
+    diag = np.diagonal(gram)
+    assert int(diag.max(initial=0)) < 2 ** 60  # the int64 combination below does not wrap
+    dist = diag[:, None] + diag[None, :] - 2 * gram
+    assert (dist >= 0).all() and not np.diagonal(dist).any()
+    return dist.tolist(), int(dist.max()), (hi - lo) ** 2
+
+
 def select(dist: np.ndarray, f: int = 2) -> list[int]:
     """Multi-Krum's selection order: NaN sorts last, ties go to the lowest client index."""
     remaining = list(range(dist.shape[0]))

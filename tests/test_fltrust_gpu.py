@@ -60,9 +60,17 @@ def device_stats(xf, xi, ref, eps=EPS, order=None) -> np.ndarray:
     own elements and nothing else."""
     n_f, n_i = xf.shape[1], xi.shape[1]
     keep, tf, ti = tables(xf, xi, order)
-    k = tf.numel()
     rf = torch.from_numpy(np.ascontiguousarray(ref[:n_f])).to(DEV)
     ri = torch.from_numpy(np.ascontiguousarray(ref[n_f:])).to(DEV)
+    got = launch_stats(tf, ti, rf, ri, eps, n_f, n_i)
+    del keep
+    return got
+
+
+def launch_stats(tf, ti, rf, ri, eps, n_f: int, n_i: int) -> np.ndarray:
+    """device_stats on pointer tables and reference halves that are on the device already, with the same
+    guards."""
+    k = tf.numel()
     nbytes = _lib.lib().plato_agg_trust_stats_workspace(k, n_f, n_i)
     assert nbytes >= (3 * k + 1) * 8
     words = (nbytes + 7) // 8
@@ -73,7 +81,6 @@ def device_stats(xf, xi, ref, eps=EPS, order=None) -> np.ndarray:
               out.data_ptr(), torch.cuda.current_stream(DEV).cuda_stream)
     torch.cuda.synchronize()
     assert bool((out[3 * k + 1:] == SENTINEL).all()) and bool((work[words:] == SENTINEL).all())
-    del keep
     return out[: 3 * k + 1].cpu().numpy()
 
 

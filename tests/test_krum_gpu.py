@@ -70,8 +70,14 @@ def tables(xf: np.ndarray, xi: np.ndarray, order=None):
 def device_sqdist(xf: np.ndarray, xi: np.ndarray, order=None) -> np.ndarray:
     """plato_agg_pairwise_sqdist on [K, n] host matrices; the output is sentinel-filled and 64 guard
     elements follow the output and the workspace: the kernels write their own elements and nothing else."""
-    n_f, n_i = xf.shape[1], xi.shape[1]
     keep, tf, ti = tables(xf, xi, order)
+    got = launch_sqdist(tf, ti, xf.shape[1], xi.shape[1])
+    del keep
+    return got
+
+
+def launch_sqdist(tf: torch.Tensor, ti: torch.Tensor, n_f: int, n_i: int) -> np.ndarray:
+    """device_sqdist on pointer tables that are on the device already, with the same guards."""
     k = tf.numel()
     nbytes = _lib.lib().plato_agg_pairwise_sqdist_workspace(k, n_f, n_i)
     assert nbytes >= 256 and nbytes % 256 == 0
@@ -81,7 +87,6 @@ def device_sqdist(xf: np.ndarray, xi: np.ndarray, order=None) -> np.ndarray:
               work.data_ptr(), out.data_ptr(), torch.cuda.current_stream(DEV).cuda_stream)
     torch.cuda.synchronize()
     assert bool((out[k * k:] == SENTINEL).all()) and bool((work[nbytes // 8:] == SENTINEL).all())
-    del keep
     return out[: k * k].cpu().numpy().reshape(k, k)
 
 
