@@ -26,17 +26,16 @@
 //    loads are issued together, the lanes that are not covered reading the box's first element and
 //    dropping it.
 //  * Nothing in the kernel is sized by K.  No count tensor: the divisor is counted in the loop.
-#include "rows.h"
+// The tile constants, the entry search, an element's result and the host side's common refusals, entry
+// walk and table upload are in boxes.h, shared with submodel.hip; here are the table rows, the coordinates
+// per number of view dims, the cover predicate, the box loop with its skips and loads, and the checks of
+// the compact box list.
+#include "boxes.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPer = 4;                        // output elements per lane
-constexpr uint64_t kTile = PLATO_AGG_ELASTIC_TILE;
-static_assert(kTile == uint64_t(kThreads) * kPer, "a tile is one pass of a workgroup");
 constexpr int kEntryWords = PLATO_AGG_ELASTIC_ENTRY_WORDS;
 constexpr int kBoxWords = PLATO_AGG_ELASTIC_BOX_WORDS;
-constexpr uint64_t kNarrow = 1ull << 30;       // entries below this many elements are indexed in 32 bits
 constexpr uint64_t kMaxBoxes = uint64_t(PLATO_AGG_ELASTIC_MAX_ENTRIES) * PLATO_AGG_ELASTIC_MAX_K;
 
 struct Entry {  // one row of the entry table
@@ -151,26 +150,15 @@ __device__ __forceinline__ void elastic_tile(const float* __restrict__ g, const 
   }
 #pragma unroll
   for (int h = 0; h < kPer; ++h)
-    if (in[h])
-      out[base + threadIdx.x + uint64_t(h) * kThreads] =
-          __fdiv_rn(__fsub_rn(acc[h], gv[h]), float(cnt[h] ? cnt[h] : 1u));
+    if (in[h]) out[base + threadIdx.x + uint64_t(h) * kThreads] = mean_of(acc[h], gv[h], cnt[h]);
 }
 
 __global__ __launch_bounds__(kThreads) void elastic_mean_kernel(const float* __restrict__ g,
                                                                const float* const* rows,
                                                                const int64_t* entries, uint32_t n_entries,
                                                                const int64_t* boxes, float* __restrict__ out) {
-  // the last entry whose first tile is at or before this workgroup's (entries without tiles share the
-  // first tile of the next entry, which comes later in the table)
   const int64_t tile = blockIdx.x;
-  uint32_t lo = 0, hi = n_entries - 1;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (sld(entries, int(mid) * kEntryWords + 5) <= tile)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
+  const uint32_t lo = find_entry<kEntryWords, 5>(entries, n_entries, tile);
   const int64_t* e = entries + uint64_t(lo) * kEntryWords;  // {out, A, B, C, D, tile0, box0, n_boxes}
   const int64_t off = sld(e, 0);
   const uint64_t A = uint64_t(sld(e, 1)), B = uint64_t(sld(e, 2)), C = uint64_t(sld(e, 3)), D = uint64_t(sld(e, 4));
@@ -194,21 +182,6 @@ __global__ __launch_bounds__(kThreads) void elastic_mean_kernel(const float* __r
 #undef ELASTIC_TILE
 }
 
-inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
-
-inline bool bad_k(int K) { return K < 1 || K > PLATO_AGG_ELASTIC_MAX_K; }
-
-// a * b * c * d if every factor and the product stay below kMaxCoords, else kMaxCoords
-inline uint64_t box_numel(int64_t a, int64_t b, int64_t c, int64_t d) {
-  uint64_t n = 1;
-  for (int64_t v : {a, b, c, d}) {
-    if (v < 0 || uint64_t(v) >= kMaxCoords) return kMaxCoords;
-    n *= uint64_t(v);
-    if (n >= kMaxCoords) return kMaxCoords;
-  }
-  return n;
-}
-
 }  // namespace
 
 extern "C" {
@@ -222,44 +195,23 @@ size_t plato_agg_elastic_tables_bytes(size_t n_entries, size_t n_boxes) {
 int plato_agg_elastic_mean(const float* d_global, const float* const* d_rows, int K, const int64_t* h_row_len,
                            const int64_t* h_entries, size_t n_entries, const int64_t* h_boxes, size_t n_boxes,
                            void* d_tables, float* d_out, size_t n_out, hipStream_t stream) {
-  const bool work = n_entries && n_out;
-  const char* why = first_refusal({
-      bad_k(K) ? "K must be in 1..4096" : nullptr,
-      n_entries > PLATO_AGG_ELASTIC_MAX_ENTRIES ? "more than 2^20 entries" : nullptr,
-      n_boxes > kMaxBoxes ? "more than 2^32 boxes" : nullptr,
-      work && (!d_global || !d_out) ? "null fp32 arena pointer" : nullptr,
-      work && (!d_rows || !h_row_len) ? "null client row table" : nullptr,
-      work && (!h_entries || (n_boxes && !h_boxes) || !d_tables) ? "null entry or box table" : nullptr,
-      work && (!aligned(d_rows, 8) || !aligned(h_row_len, 8) || !aligned(h_entries, 8) || !aligned(h_boxes, 8))
-          ? "pointer tables must be 8-byte aligned"
-          : nullptr,
-      work && !aligned(d_tables, 256) ? "the device tables must be 256-byte aligned" : nullptr,
-      work && !aligned(d_global, 4) ? "the global region must be 4-byte aligned" : nullptr,
-      work ? bad_outputs(n_out, d_out, 0, nullptr) : nullptr,
-      too_many_coords(n_out, 0),
-  });
+  const char* why = bad_box_args(d_global, d_rows, K, h_row_len, h_entries, n_entries, h_boxes, n_boxes != 0,
+                                 n_boxes > kMaxBoxes ? "more than 2^32 boxes" : nullptr, d_tables, d_out, n_out);
   if (why) return fail(PLATO_AGG_EINVAL, why);
-  if (!work) return plato_agg_internal::clear_error();
+  if (!n_entries || !n_out) return plato_agg_internal::clear_error();
 
-  for (int k = 0; k < K; ++k)
-    if (h_row_len[k] < 0 || uint64_t(h_row_len[k]) >= kMaxCoords)
-      return fail(PLATO_AGG_EINVAL, "client " + std::to_string(k) + ": row length outside [0, 2^38)");
+  if (const int bad = check_row_lengths(K, h_row_len)) return bad;
   const Entry* entries = reinterpret_cast<const Entry*>(h_entries);
   const Box* boxes = reinterpret_cast<const Box*>(h_boxes);
-  uint64_t tiles = 0, end = 0, listed = 0;
+  EntryWalk walk;
+  uint64_t listed = 0;
   for (size_t e = 0; e < n_entries; ++e) {
     const Entry& en = entries[e];
     const std::string at = "entry " + std::to_string(e);
-    const uint64_t n = box_numel(en.A, en.B, en.C, en.D);
-    if (n >= kMaxCoords) return fail(PLATO_AGG_EINVAL, at + ": bad view extents");
-    if (en.out < 0 || uint64_t(en.out) < end || uint64_t(en.out) + n > n_out)
-      return fail(PLATO_AGG_EINVAL, at + ": output range outside the region or overlapping the entry before it");
-    if (en.tile0 < 0 || uint64_t(en.tile0) != tiles)
-      return fail(PLATO_AGG_EINVAL, at + ": first tile is not the number of tiles before it");
+    why = walk.next(en.out, box_numel({en.A, en.B, en.C, en.D}), en.tile0, 0, n_out);
+    if (why) return fail(PLATO_AGG_EINVAL, at + why);
     if (en.box0 < 0 || uint64_t(en.box0) != listed || en.n_boxes < 0 || uint64_t(en.n_boxes) > n_boxes - listed)
       return fail(PLATO_AGG_EINVAL, at + ": box range does not follow the entry before it inside the box table");
-    end = uint64_t(en.out) + n;
-    tiles += (n + kTile - 1) / kTile;
     int64_t before = -1;
     for (uint64_t x = listed; x < listed + uint64_t(en.n_boxes); ++x) {
       const Box& b = boxes[x];
@@ -269,31 +221,21 @@ int plato_agg_elastic_mean(const float* d_global, const float* const* d_rows, in
       before = b.client;
       if (b.a < 0 || b.b < 0 || b.c < 0 || b.d < 0 || b.a > en.A || b.b > en.B || b.c > en.C || b.d > en.D)
         return fail(PLATO_AGG_EINVAL, who + ": box extent above the entry's extent");
-      const uint64_t m = box_numel(b.a, b.b, b.c, b.d);  // <= n
-      const uint64_t len = uint64_t(h_row_len[b.client]);
-      if (b.src < 0 || uint64_t(b.src) > len || m > len - uint64_t(b.src))
+      if (past_row(b.src, box_numel({b.a, b.b, b.c, b.d}), h_row_len[b.client]))  // at most the entry's elements
         return fail(PLATO_AGG_EINVAL, who + ": box runs past the client's row length");
     }
     listed += uint64_t(en.n_boxes);
   }
   if (listed != n_boxes) return fail(PLATO_AGG_EINVAL, "the entries' box ranges end before the box table does");
-  if (!tiles) return plato_agg_internal::clear_error();  // every entry is empty
+  if (!walk.tiles) return plato_agg_internal::clear_error();  // every entry is empty
 
-  // the tables, behind the caller's earlier work on the stream; the caller keeps its host tables
-  // unchanged until the stream has passed this call
-  char* dev = static_cast<char*>(d_tables);
-  const size_t entry_bytes = n_entries * sizeof(Entry);
-  Box* d_boxes = reinterpret_cast<Box*>(dev + round_up(entry_bytes, 256));
-  hipError_t err = hipMemcpyAsync(dev, h_entries, entry_bytes, hipMemcpyHostToDevice, stream);
-  if (err == hipSuccess && n_boxes)
-    err = hipMemcpyAsync(d_boxes, h_boxes, n_boxes * sizeof(Box), hipMemcpyHostToDevice, stream);
-  if (err != hipSuccess) return fail(PLATO_AGG_EHIP, std::string("elastic_mean tables: ") + hipGetErrorString(err));
-  hipLaunchKernelGGL(elastic_mean_kernel, dim3(uint32_t(tiles)), dim3(kThreads), 0, stream, d_global, d_rows,
-                     reinterpret_cast<const int64_t*>(dev), uint32_t(n_entries),
-                     reinterpret_cast<const int64_t*>(d_boxes), d_out);
-  err = hipGetLastError();
-  if (err != hipSuccess) return fail(PLATO_AGG_EHIP, std::string("elastic_mean: ") + hipGetErrorString(err));
-  return plato_agg_internal::clear_error();
+  const int64_t* d_boxes;
+  if (const int bad = upload_and_check("elastic_mean", d_tables, h_entries, n_entries * sizeof(Entry), h_boxes,
+                                       n_boxes * sizeof(Box), stream, &d_boxes))
+    return bad;
+  hipLaunchKernelGGL(elastic_mean_kernel, dim3(uint32_t(walk.tiles)), dim3(kThreads), 0, stream, d_global, d_rows,
+                     static_cast<const int64_t*>(d_tables), uint32_t(n_entries), d_boxes, d_out);
+  return launched("elastic_mean");
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // C-ABI entry points refuse the same malformed arguments with the same words.  Everything is in the
 // anonymous namespace, as it was in each of the three files: the kernels' symbols do not change.
 // (Not shared: median_kernel / nearest_mean_kernel's load and select, see robust.hip and DESIGN.md §17.)
-// submodel.hip takes the table loads and the refusals from here; its rows have lengths of their own.
+// submodel.hip and elastic.hip take the table loads and the refusals from here, through boxes.h, which
+// holds what only those two share; their rows have lengths of their own.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -20,7 +20,6 @@ integer entries of rank >= 1, several GPUs, bf16 and QSGD payloads.
 
 from __future__ import annotations
 
-import time
 from collections import OrderedDict
 from typing import Mapping, Sequence
 
@@ -29,7 +28,7 @@ import torch
 
 from . import _lib
 from .arena import ArenaLayout, payload_codec
-from .submodel import ROW_ALIGN, _State, _numel
+from .submodel import ROW_ALIGN, _BoxRound, _BoxTables, _numel, compact_layout  # noqa: F401  (this module's too)
 
 MAX_K = _lib.PLATO_AGG_ELASTIC_MAX_K
 TILE = _lib.PLATO_AGG_ELASTIC_TILE
@@ -83,11 +82,6 @@ def client_signature(glayout: ArenaLayout, payload: Mapping[str, torch.Tensor], 
     return tuple(sig)
 
 
-def compact_layout(signature: tuple) -> ArenaLayout:
-    """A client's held entries of rank >= 1 packed back to back: its row."""
-    return ArenaLayout.from_shapes([(name, shape, "f32") for name, shape in signature])
-
-
 def canonical_view(shape: tuple, rank: int, holders: Sequence[tuple]) -> tuple[tuple, list]:
     """``([A, B, C, D], groups)`` of an entry of ``shape`` and rank ``rank`` whose holders have the shapes
     ``holders``.  ``groups`` lists the entry's dims per view dim, right-aligned (the leading view dims are 1).
@@ -114,29 +108,15 @@ def client_box(gshape: tuple, groups: list, cshape: tuple, what: str) -> tuple:
     return (1,) * (4 - len(box)) + box
 
 
-class ElasticTables:
-    """The host tables of one ``plato_agg_elastic_mean`` call (include/plato_agg.h)."""
+class ElasticTables(_BoxTables):
+    """The host tables of one ``plato_agg_elastic_mean`` call: the compact box list [boxes, 6]."""
 
-    def __init__(self, entries: np.ndarray, boxes: np.ndarray, row_len: np.ndarray, n_out: int):
-        self.entries, self.boxes, self.row_len, self.n_out = entries, boxes, row_len, n_out
-
-    @property
-    def k(self) -> int:
-        return int(self.row_len.shape[0])
-
-    def covered(self) -> int:
-        """Client elements the kernel reads: the sum of the boxes."""
-        b = self.boxes
-        return int((b[:, 0] * b[:, 1] * b[:, 2] * b[:, 3]).sum())  # every box is below 2^38 elements
+    EXTENTS = 4
 
     def absent_share(self) -> float:
         """The share of (entry, client) pairs without a box: what the compact list leaves out."""
         pairs = len(self.entries) * self.k
         return 1.0 - len(self.boxes) / pairs if pairs else 0.0
-
-    def algorithmic_bytes(self) -> int:
-        """The global region read and the result written once, every covered client element read once."""
-        return 4 * (2 * self.n_out + self.covered())
 
 
 def build_tables(glayout: ArenaLayout, signatures: Sequence[tuple], update_track: bool = True) -> ElasticTables:
@@ -172,129 +152,34 @@ def check_payloads(payloads: Sequence[Mapping[str, torch.Tensor]]) -> None:
             raise ValueError(f"elastic aggregation takes native payloads; weights_received[{i}] holds {codec} codes")
 
 
-class ElasticRound:
-    """One elastic aggregation on a ``FedAvgEngine``: every refusal in the constructor (no GPU work), then
-    :meth:`stage` (pinned packs and H2D copies on the copy stream), :meth:`launch`, :meth:`result`."""
+class ElasticRound(_BoxRound):
+    """One elastic aggregation (``plato_amd.submodel._BoxRound``); every result is float32, an integer
+    counter zeros of its shape."""
+
+    KIND, SLOT, KERNEL = "elastic", "_elastic", "elastic_mean"
 
     def __init__(self, engine, global_model: Mapping[str, torch.Tensor],
                  payloads: Sequence[Mapping[str, torch.Tensor]], update_track: bool = True):
-        if getattr(engine, "primary", None) is not None:
-            raise NotImplementedError("elastic aggregation runs on one GPU: use FedAvgEngine")
-        check_payloads(payloads)
-        self.engine, self.update_track = engine, bool(update_track)
-        self.global_model, self.payloads = global_model, list(payloads)
-        self.glayout, self.zeros = global_layout(global_model)
-        self.signatures = [client_signature(self.glayout, p, self.update_track, f"weights_received[{i}]")
-                           for i, p in enumerate(self.payloads)]
-        self.tables = build_tables(self.glayout, self.signatures, self.update_track)
-        self.timings: dict = {}
-        self._timers: list = []
-        self._t0 = time.perf_counter()
-        self.event = None
-        self._out = None
-        self._keep = None
+        self.update_track = bool(update_track)
+        super().__init__(engine, global_model, payloads)
 
-    # ---------------------------------------------------------------- staging
-    def _state(self) -> _State:
-        st = getattr(self.engine, "_elastic", None)
-        if st is None:
-            st = self.engine._elastic = _State()
-        return st
+    def _check(self) -> tuple:
+        check_payloads(self.payloads)
+        glayout, self.zeros = global_layout(self.global_model)
+        signatures = [client_signature(glayout, p, self.update_track, f"weights_received[{i}]")
+                      for i, p in enumerate(self.payloads)]
+        return glayout, signatures, build_tables(glayout, signatures, self.update_track)
 
-    def _stager(self, st: _State, layout: ArenaLayout):
-        from .engine import _Stager
+    def _tables_bytes(self) -> int:
+        return _lib.lib().plato_agg_elastic_tables_bytes(len(self.tables.entries), len(self.tables.boxes))
 
-        hit = st.stagers.get(layout.signature)
-        if hit is None:
-            hit = st.stagers[layout.signature] = _Stager(layout, self.engine.device, depth=2,
-                                                         stream=self.engine._copy_stream)
-        return hit
+    def _mean(self, d_global, d_rows, h_entries, h_boxes, d_tables, d_out, stream) -> None:
+        tab = self.tables
+        _lib.call("plato_agg_elastic_mean", d_global, d_rows, tab.k, tab.row_len.ctypes.data, h_entries,
+                  len(tab.entries), h_boxes, len(tab.boxes), d_tables, d_out, tab.n_out, stream)
 
-    def stage(self) -> None:
-        """The global model's float32 entries and every client's row to HBM: one pinned pack and one copy
-        each, on the engine's copy stream.  Clients of one shape signature share a layout and a stager."""
-        eng, st, dev = self.engine, self._state(), self.engine.device
-        if eng._copy_stream is None:
-            eng._copy_stream = torch.cuda.Stream(dev)
-        # an earlier round's kernel may still read the slab and the global arena
-        eng._copy_stream.wait_stream(torch.cuda.current_stream(dev))
-        self.glayout = st.globals.setdefault(self.glayout.signature, self.glayout)  # keeps its result pool
-        n = self.glayout.n_f32
-        if st.global_dev is None or st.global_dev.numel() < max(n, 1):
-            st.global_dev = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        if n:
-            self._stager(st, self.glayout).put(self.global_model, st.global_dev, None)
-        offsets, at = [], 0
-        for sig in self.signatures:
-            if sig not in st.layouts:
-                st.layouts[sig] = compact_layout(sig)
-            offsets.append(at)
-            at += -(-st.layouts[sig].n_f32 // ROW_ALIGN) * ROW_ALIGN
-        if st.slab is None or st.slab.numel() < max(at, 1):
-            st.slab = torch.empty(max(at, 1), dtype=torch.float32, device=dev)
-        for off, sig, payload in zip(offsets, self.signatures, self.payloads):
-            lay = st.layouts[sig]
-            if lay.n_f32:
-                self._stager(st, lay).put(payload, st.slab[off:off + lay.n_f32], None)
-        self._row_ptrs = np.asarray([st.slab.data_ptr() + 4 * off for off in offsets], dtype=np.int64)
-        self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
-
-    # ----------------------------------------------------------------- launch
-    def _timed(self, name: str, stream):
-        from .engine import _KernelTimer
-
-        return _KernelTimer(self, name, stream)
-
-    def launch(self) -> None:
-        eng, st, dev, tab = self.engine, self._state(), self.engine.device, self.tables
-        stream = torch.cuda.current_stream(dev)
-        stream.wait_stream(eng._copy_stream)
-        n = tab.n_out
-        out = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        rows = torch.from_numpy(self._row_ptrs).to(dev)
-        nbytes = _lib.lib().plato_agg_elastic_tables_bytes(len(tab.entries), len(tab.boxes))
-        d_tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        # pinned: the call's copies of the tables are stream-ordered, and the round keeps them until result()
-        h_entries = torch.from_numpy(tab.entries).pin_memory()
-        h_boxes = torch.from_numpy(tab.boxes).pin_memory() if len(tab.boxes) else None
-        with self._timed("elastic_mean", stream):
-            _lib.call("plato_agg_elastic_mean", st.global_dev.data_ptr(), rows.data_ptr(), tab.k,
-                      tab.row_len.ctypes.data, h_entries.data_ptr(), len(tab.entries),
-                      h_boxes.data_ptr() if h_boxes is not None else None, len(tab.boxes),
-                      d_tables.data_ptr(), out.data_ptr(), n, stream.cuda_stream)
-        host = eng._result_pool(self.glayout).get()[0]
-        host.copy_(out[:n], non_blocking=True)
-        self.event = torch.cuda.Event(enable_timing=True)
-        self.event.record(stream)
-        self._out = host
-        self._keep = (out, rows, d_tables, h_entries, h_boxes)
-
-    def _resolve_timers(self) -> None:
-        for name, e0, e1 in self._timers:
-            self.timings[name + "_ms"] = e0.elapsed_time(e1)
-        self._timers = []
-
-    def wait(self) -> None:
-        if self.event is None:
-            raise RuntimeError("launch() first")
-        self.event.synchronize()
-
-    def algorithmic_bytes(self) -> int:
-        return self.tables.algorithmic_bytes()
-
-    def result(self) -> "OrderedDict[str, torch.Tensor]":
-        """CPU float32 tensors in the global model's key order: the float32 entries from the device, the
-        integer counters as zeros of their shape."""
-        self.wait()
-        self._resolve_timers()
-        self.timings["kernel_ms"] = self.timings.get("elastic_mean_ms")
-        self.timings["total_ms"] = (time.perf_counter() - self._t0) * 1e3
-        host, self._out, self._keep = self._out, None, None
-        mine = self.glayout.unpack(host, None)
-        out = OrderedDict()
-        for name, tensor in self.global_model.items():
-            out[name] = mine[name] if name in mine else torch.zeros(tensor.shape, dtype=torch.float32)
-        return out
+    def _absent(self, tensor: torch.Tensor) -> torch.Tensor:
+        return torch.zeros(tensor.shape, dtype=torch.float32)
 
 
 class ElasticAggregates:

@@ -16,30 +16,13 @@ the engine takes the flag (``FedAvgEngine.aggregate_elastic``), nothing here pas
 
 from __future__ import annotations
 
-from .. import tracing
-from .fedavg import _EngineHolder
+from .submodel import _BoxAggregationMixin
 
 
-class ElasticAggregationMixin(_EngineHolder):
+class ElasticAggregationMixin(_BoxAggregationMixin):
     """``aggregate_weights`` hook of the sysheterofl server, on one GPU."""
 
-    async def aggregate_weights(self, updates, baseline_weights, weights_received):
-        # baseline_weights is not read: the reference aggregates on top of algorithm.model's state_dict
-        engine = self.aggregation_engine()
-        if getattr(engine, "primary", None) is not None:
-            raise NotImplementedError("elastic aggregation runs on one GPU (aggregation_devices has several)")
-        try:
-            rnd = engine.begin_elastic(self.algorithm.model.state_dict(), weights_received)
+    _kind = "elastic"
 
-            def stage():
-                with tracing.range("plato_amd.stage"):
-                    rnd.stage()
-
-            await self._off_loop(stage)
-            with tracing.range("plato_amd.launch"):
-                rnd.launch()
-            with tracing.range("plato_amd.fetch"):
-                return await self._finish(rnd)
-        finally:
-            # payloads of the full model may have been staged at arrival: their slots go back unused
-            engine.release_arrivals()
+    def _begin_round(self, engine, state_dict, weights_received):
+        return engine.begin_elastic(state_dict, weights_received)

@@ -19,19 +19,22 @@ from .. import tracing
 from .fedavg import _EngineHolder
 
 
-class SubmodelAggregationMixin(_EngineHolder):
-    """``aggregate_weights`` hook of the sub-model servers, on one GPU."""
+class _BoxAggregationMixin(_EngineHolder):
+    """``aggregate_weights`` hook of the model-search servers, on one GPU: a kind names itself and begins
+    its round (``plato_amd.servers.elastic`` has the other one)."""
 
-    #: "heterofl" (HeteroFL, FjORD) or "fedrolex" (FedRolex, AnyCostFL): plato_amd.submodel.RULES
-    submodel_rule = "heterofl"
+    _kind: str
+
+    def _begin_round(self, engine, state_dict, weights_received):
+        raise NotImplementedError
 
     async def aggregate_weights(self, updates, baseline_weights, weights_received):
         # baseline_weights is not read: the reference aggregates on top of algorithm.model's state_dict
         engine = self.aggregation_engine()
         if getattr(engine, "primary", None) is not None:
-            raise NotImplementedError("sub-model aggregation runs on one GPU (aggregation_devices has several)")
+            raise NotImplementedError(f"{self._kind} aggregation runs on one GPU (aggregation_devices has several)")
         try:
-            rnd = engine.begin_submodels(self.algorithm.model.state_dict(), weights_received, self.submodel_rule)
+            rnd = self._begin_round(engine, self.algorithm.model.state_dict(), weights_received)
 
             def stage():
                 with tracing.range("plato_amd.stage"):
@@ -43,5 +46,16 @@ class SubmodelAggregationMixin(_EngineHolder):
             with tracing.range("plato_amd.fetch"):
                 return await self._finish(rnd)
         finally:
-            # payloads of the full width may have been staged at arrival: their slots go back unused
+            # payloads of the full model may have been staged at arrival: their slots go back unused
             engine.release_arrivals()
+
+
+class SubmodelAggregationMixin(_BoxAggregationMixin):
+    """``aggregate_weights`` hook of the sub-model servers, on one GPU."""
+
+    #: "heterofl" (HeteroFL, FjORD) or "fedrolex" (FedRolex, AnyCostFL): plato_amd.submodel.RULES
+    submodel_rule = "heterofl"
+    _kind = "sub-model"
+
+    def _begin_round(self, engine, state_dict, weights_received):
+        return engine.begin_submodels(state_dict, weights_received, self.submodel_rule)

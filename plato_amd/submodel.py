@@ -15,8 +15,9 @@ the global ``state_dict`` and the clients' in arrival order, for every key of G 
 
 The tables of :func:`build_tables` are pure numpy; :class:`SubmodelRound` stages and launches.  Out of
 scope: ``sysheterofl`` (boxes on four dims, keys missing per client, int64 counters divided as floats: it
-is ``plato_amd.elastic``, with an entry point and tables of its own), several GPUs, bf16 and QSGD
-payloads, and rows prestaged at arrival (sub-model payloads are staged here).
+is ``plato_amd.elastic``, with an entry point and a table format of its own; its tables and its round are
+the classes here, :class:`_BoxTables` and :class:`_BoxRound`, with what differs filled in), several GPUs,
+bf16 and QSGD payloads, and rows prestaged at arrival (sub-model payloads are staged here).
 """
 
 from __future__ import annotations
@@ -92,7 +93,7 @@ def client_signature(glayout: ArenaLayout, rule: str, payload: Mapping[str, torc
 
 
 def compact_layout(signature: tuple) -> ArenaLayout:
-    """A client's participating entries packed back to back: its row."""
+    """A client's entries that the aggregation reads, packed back to back: its row."""
     return ArenaLayout.from_shapes([(name, shape, "f32") for name, shape in signature])
 
 
@@ -123,8 +124,10 @@ def client_box(gshape: tuple, rank: int, cshape: tuple, what: str) -> tuple[int,
     return int(cshape[0]), int(cshape[1]), int(cshape[2])
 
 
-class SubmodelTables:
-    """The host tables of one ``plato_agg_submodel_mean`` call (include/plato_agg.h)."""
+class _BoxTables:
+    """The host tables of one call (include/plato_agg.h); a box row begins with its ``EXTENTS`` extents."""
+
+    EXTENTS: int
 
     def __init__(self, entries: np.ndarray, boxes: np.ndarray, row_len: np.ndarray, n_out: int):
         self.entries, self.boxes, self.row_len, self.n_out = entries, boxes, row_len, n_out
@@ -135,12 +138,17 @@ class SubmodelTables:
 
     def covered(self) -> int:
         """Client elements the kernel reads: the sum of the boxes."""
-        b = self.boxes
-        return int((b[..., 0] * b[..., 1] * b[..., 2]).sum())  # every box is below 2^38 elements
+        return int(self.boxes[..., :self.EXTENTS].prod(axis=-1).sum())  # every box is below 2^38 elements
 
     def algorithmic_bytes(self) -> int:
         """The global region read and the result written once, every covered client element read once."""
         return 4 * (2 * self.n_out + self.covered())
+
+
+class SubmodelTables(_BoxTables):
+    """The host tables of one ``plato_agg_submodel_mean`` call: boxes [entries, K, 4]."""
+
+    EXTENTS = 3
 
 
 def build_tables(glayout: ArenaLayout, signatures: Sequence[tuple], rule: str) -> SubmodelTables:
@@ -195,19 +203,21 @@ class _State:
         self.global_dev: torch.Tensor | None = None
 
 
-class SubmodelRound:
-    """One sub-model aggregation on a ``FedAvgEngine``: every refusal in the constructor (no GPU work),
-    then :meth:`stage` (pinned packs and H2D copies on the copy stream), :meth:`launch`, :meth:`result`."""
+class _BoxRound:
+    """One aggregation of leading-corner boxes on a ``FedAvgEngine``: every refusal in the constructor (no
+    GPU work), then :meth:`stage` (pinned packs and H2D copies on the copy stream), :meth:`launch`,
+    :meth:`result`.  A kind (:class:`SubmodelRound`, ``plato_amd.elastic.ElasticRound``) gives KIND for the
+    messages, SLOT (the engine attribute that keeps its :class:`_State`: a slab and stagers per kind) and
+    KERNEL for the timings; ``_check()``, the other refusals, returning (global layout, signatures, tables);
+    ``_tables_bytes()`` and ``_mean(...)``, the library calls over ``self.tables`` (pointers as integers,
+    ``h_boxes`` None without boxes); and ``_absent(tensor)``, the result for a key the device did not produce."""
 
     def __init__(self, engine, global_model: Mapping[str, torch.Tensor],
-                 payloads: Sequence[Mapping[str, torch.Tensor]], rule: str = "heterofl"):
-        check_payloads(payloads, rule)
-        self.engine, self.rule = engine, rule
-        self.global_model, self.payloads = global_model, list(payloads)
-        self.glayout = global_layout(global_model)
-        self.signatures = [client_signature(self.glayout, rule, p, f"weights_received[{i}]")
-                           for i, p in enumerate(self.payloads)]
-        self.tables = build_tables(self.glayout, self.signatures, rule)
+                 payloads: Sequence[Mapping[str, torch.Tensor]]):
+        if getattr(engine, "primary", None) is not None:
+            raise NotImplementedError(f"{self.KIND} aggregation runs on one GPU: use FedAvgEngine")
+        self.engine, self.global_model, self.payloads = engine, global_model, list(payloads)
+        self.glayout, self.signatures, self.tables = self._check()
         self.timings: dict = {}
         self._timers: list = []
         self._t0 = time.perf_counter()
@@ -217,9 +227,10 @@ class SubmodelRound:
 
     # ---------------------------------------------------------------- staging
     def _state(self) -> _State:
-        st = getattr(self.engine, "_submodel", None)
+        st = getattr(self.engine, self.SLOT, None)
         if st is None:
-            st = self.engine._submodel = _State()
+            st = _State()
+            setattr(self.engine, self.SLOT, st)
         return st
 
     def _stager(self, st: _State, layout: ArenaLayout):
@@ -232,8 +243,8 @@ class SubmodelRound:
         return hit
 
     def stage(self) -> None:
-        """The global model's participating entries and every client's row to HBM: one pinned pack and
-        one copy each, on the engine's copy stream."""
+        """The global model's entries on the device and every client's row to HBM: one pinned pack and one
+        copy each, on the engine's copy stream.  Clients of one shape signature share a layout and a stager."""
         eng, st, dev = self.engine, self._state(), self.engine.device
         if eng._copy_stream is None:
             eng._copy_stream = torch.cuda.Stream(dev)
@@ -273,15 +284,14 @@ class SubmodelRound:
         n = tab.n_out
         out = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
         rows = torch.from_numpy(self._row_ptrs).to(dev)
-        nbytes = _lib.lib().plato_agg_submodel_tables_bytes(tab.k, len(tab.entries))
-        d_tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        d_tables = torch.empty(self._tables_bytes(), dtype=torch.uint8, device=dev)
         # pinned: the call's copies of the tables are stream-ordered, and the round keeps them until result()
         h_entries = torch.from_numpy(tab.entries).pin_memory()
-        h_boxes = torch.from_numpy(tab.boxes).pin_memory()
-        with self._timed("submodel_mean", stream):
-            _lib.call("plato_agg_submodel_mean", st.global_dev.data_ptr(), rows.data_ptr(), tab.k,
-                      tab.row_len.ctypes.data, h_entries.data_ptr(), h_boxes.data_ptr(), len(tab.entries),
-                      d_tables.data_ptr(), out.data_ptr(), n, stream.cuda_stream)
+        h_boxes = torch.from_numpy(tab.boxes).pin_memory() if tab.boxes.size else None
+        with self._timed(self.KERNEL, stream):
+            self._mean(st.global_dev.data_ptr(), rows.data_ptr(), h_entries.data_ptr(),
+                       h_boxes.data_ptr() if h_boxes is not None else None, d_tables.data_ptr(), out.data_ptr(),
+                       stream.cuda_stream)
         host = eng._result_pool(self.glayout).get()[0]
         host.copy_(out[:n], non_blocking=True)
         self.event = torch.cuda.Event(enable_timing=True)
@@ -303,18 +313,48 @@ class SubmodelRound:
         return self.tables.algorithmic_bytes()
 
     def result(self) -> "OrderedDict[str, torch.Tensor]":
-        """CPU tensors in the global model's key order: participating entries float32 from the device,
-        the others clones of the global model's."""
+        """CPU tensors in the global model's key order: the entries on the device float32 from there, the
+        others as :meth:`_absent` gives them."""
         self.wait()
         self._resolve_timers()
-        self.timings["kernel_ms"] = self.timings.get("submodel_mean_ms")
+        self.timings["kernel_ms"] = self.timings.get(self.KERNEL + "_ms")
         self.timings["total_ms"] = (time.perf_counter() - self._t0) * 1e3
         host, self._out, self._keep = self._out, None, None
         mine = self.glayout.unpack(host, None)
         out = OrderedDict()
         for name, tensor in self.global_model.items():
-            out[name] = mine[name] if name in mine else tensor.detach().clone()
+            out[name] = mine[name] if name in mine else self._absent(tensor)
         return out
+
+
+class SubmodelRound(_BoxRound):
+    """One sub-model aggregation (:class:`_BoxRound`); an entry that passes through is a clone of the
+    global model's."""
+
+    KIND, SLOT, KERNEL = "sub-model", "_submodel", "submodel_mean"
+
+    def __init__(self, engine, global_model: Mapping[str, torch.Tensor],
+                 payloads: Sequence[Mapping[str, torch.Tensor]], rule: str = "heterofl"):
+        self.rule = rule
+        super().__init__(engine, global_model, payloads)
+
+    def _check(self) -> tuple:
+        check_payloads(self.payloads, self.rule)
+        glayout = global_layout(self.global_model)
+        signatures = [client_signature(glayout, self.rule, p, f"weights_received[{i}]")
+                      for i, p in enumerate(self.payloads)]
+        return glayout, signatures, build_tables(glayout, signatures, self.rule)
+
+    def _tables_bytes(self) -> int:
+        return _lib.lib().plato_agg_submodel_tables_bytes(self.tables.k, len(self.tables.entries))
+
+    def _mean(self, d_global, d_rows, h_entries, h_boxes, d_tables, d_out, stream) -> None:
+        tab = self.tables
+        _lib.call("plato_agg_submodel_mean", d_global, d_rows, tab.k, tab.row_len.ctypes.data, h_entries, h_boxes,
+                  len(tab.entries), d_tables, d_out, tab.n_out, stream)
+
+    def _absent(self, tensor: torch.Tensor) -> torch.Tensor:
+        return tensor.detach().clone()
 
 
 class SubmodelAggregates:
