@@ -380,6 +380,12 @@ int plato_agg_weighted_sum_f64(const double* const* d_x, const double* d_w, int 
  * and divides all but the first by -lr (examples/server_aggregation/fedadp/
  * fedadp_server.py:122-133, RAW for the global gradient, DELTA for a client).
  * d_src_*: K device pointers; d_out: K device pointers to n_flat floats.
+ * Delta arenas: in PLATO_AGG_FLAT_DELTA, d_base_f32 = d_base_i64 = NULL means the
+ * sources already hold x - b (fp32 differences, int64 wrapping differences:
+ * compute_weight_deltas, plato/algorithms/fedavg.py:13-27, formed when each payload
+ * was staged); the values are the same (x - (+0) for fp32, x - 0 for int64), and the
+ * kernel reads no baseline.  One of the two NULL, or a NULL baseline in
+ * PLATO_AGG_FLAT_CAST_DIFF, is PLATO_AGG_EINVAL.
  */
 typedef struct plato_agg_segment {
   uint64_t flat_offset;

@@ -297,6 +297,15 @@ class ArenaLayout:
         return out
 
 
+class DeviceArena:
+    """One model arena in HBM: fp32 region + int64 region (+ fp32 view of int64 results)."""
+
+    def __init__(self, layout: ArenaLayout, device: torch.device, i64_dtype: torch.dtype = torch.int64):
+        self.layout = layout
+        self.f32 = torch.empty(layout.row_f32, dtype=torch.float32, device=device)
+        self.i64 = torch.empty(layout.row_i64, dtype=i64_dtype, device=device)
+
+
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 

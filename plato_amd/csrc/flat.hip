@@ -85,10 +85,18 @@ struct FlatBase {
   int64_t i;
 };
 
+// DELTA with a NULL baseline (delta arenas: the sources hold x - b): +0 / 0 is subtracted and nothing is
+// loaded.  A mode of its own, chosen once per launch from the kernel arguments, so that the loops of the
+// other modes carry no test of the pointer (measured: a select inside flat_base cost the weight-arena
+// flatten 3-5 %).
+constexpr int kFlatDeltaNoBase = 3;
+static_assert(kFlatDeltaNoBase != PLATO_AGG_FLAT_DELTA && kFlatDeltaNoBase != PLATO_AGG_FLAT_CAST_DIFF &&
+              kFlatDeltaNoBase != PLATO_AGG_FLAT_RAW, "a private mode, never one the entry point accepts");
+
 template <int MODE, bool I64>
 __device__ __forceinline__ FlatBase flat_base(const FlatArgs& a, uint64_t e) {
   FlatBase b{0.f, 0};
-  if (MODE != PLATO_AGG_FLAT_RAW) {
+  if (MODE == PLATO_AGG_FLAT_DELTA || MODE == PLATO_AGG_FLAT_CAST_DIFF) {
     if (!I64) b.f = a.base_f[e];
     else b.i = a.base_i[e];
   }
@@ -182,8 +190,10 @@ __global__ __launch_bounds__(256) void flatten_kernel(FlatArgs a) {
     flat_block<PLATO_AGG_FLAT_RAW>(a, k0, nk, b0, b1);
   } else if (a.mode == PLATO_AGG_FLAT_CAST_DIFF) {
     flat_block<PLATO_AGG_FLAT_CAST_DIFF>(a, k0, nk, b0, b1);
-  } else {
+  } else if (a.base_f) {
     flat_block<PLATO_AGG_FLAT_DELTA>(a, k0, nk, b0, b1);
+  } else {
+    flat_block<kFlatDeltaNoBase>(a, k0, nk, b0, b1);
   }
 }
 
@@ -1809,8 +1819,10 @@ int plato_agg_flatten(int mode, const void* const* d_src_f32, const void* const*
   if (n_flat == 0) return clear_error();
   if (!d_src_f32 || !d_src_i64 || !d_segs || !n_segs || !d_out)
     return set_error(PLATO_AGG_EINVAL, "null pointer");
-  if (mode != PLATO_AGG_FLAT_RAW && (!d_base_f32 || !d_base_i64))
-    return set_error(PLATO_AGG_EINVAL, "the delta modes need the baseline");
+  if (mode == PLATO_AGG_FLAT_CAST_DIFF && (!d_base_f32 || !d_base_i64))
+    return set_error(PLATO_AGG_EINVAL, "CAST_DIFF needs the baseline");
+  if (mode == PLATO_AGG_FLAT_DELTA && !d_base_f32 != !d_base_i64)
+    return set_error(PLATO_AGG_EINVAL, "DELTA takes both baseline regions or neither (delta arenas)");
   FlatArgs a{};
   a.src_f = d_src_f32;
   a.src_i = d_src_i64;

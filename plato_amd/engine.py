@@ -29,9 +29,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arena import CODECS, F32, I64, ArenaLayout, fedadp_order, payload_codec, same_f32_bits
+from .arena import CODECS, F32, I64, ArenaLayout, DeviceArena, payload_codec, same_f32_bits
 from .arrivals import Adopt, ArrivalTable, adopt_rule
 from .elastic import ElasticAggregates
+from .reductions import VariantLaunches
 from .robust import RobustAggregates, RobustLaunches
 from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key, payload_fingerprint
 from .submodel import SubmodelAggregates
@@ -70,21 +71,21 @@ def require_device(device=None) -> torch.device:
     return dev
 
 
+def staged_slots(capacity: int, staged: Sequence[bool], slots: Sequence[int]) -> list[int]:
+    """``slots`` as a list, every one of them in range and staged (single- and multi-GPU rounds)."""
+    slots = list(slots)
+    for slot in slots:
+        if not (0 <= slot < capacity and staged[slot]):
+            raise ValueError(f"client slot {slot} was not staged")
+    return slots
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
 def _stream_handle(stream: torch.cuda.Stream) -> int:
     return stream.cuda_stream
-
-
-class DeviceArena:
-    """One model arena in HBM: fp32 region + int64 region (+ fp32 view of int64 results)."""
-
-    def __init__(self, layout: ArenaLayout, device: torch.device, i64_dtype: torch.dtype = torch.int64):
-        self.layout = layout
-        self.f32 = torch.empty(layout.row_f32, dtype=torch.float32, device=device)
-        self.i64 = torch.empty(layout.row_i64, dtype=i64_dtype, device=device)
 
 
 class ClientSlab:
@@ -601,9 +602,10 @@ class _KernelTimer:
         return False
 
 
-class AggregationRound(RobustLaunches):
-    """One aggregation: client rows staged H2D (in any order), then one launch (``launch_robust`` and the
-    other robust launches: ``plato_amd.robust``).
+class AggregationRound(RobustLaunches, VariantLaunches):
+    """One aggregation: client rows staged H2D (in any order), then one launch: the FedAvg sums here, the
+    robust aggregators in ``plato_amd.robust``, the variant servers' reductions in ``plato_amd.reductions``.
+    Every launch over staged rows starts from :meth:`_staged_rows`.
 
     Rows are slots; the summation order is given at :meth:`launch` time by
     ``order`` (default: slot order), matching ``self.updates`` order in the
@@ -757,9 +759,7 @@ class AggregationRound(RobustLaunches):
         order = list(range(len(weights))) if order is None else list(order)
         if len(order) != len(weights):
             raise ValueError("order and weights must have the same length")
-        for slot in order:
-            if not (0 <= slot < self.capacity and self.staged[slot]):
-                raise ValueError(f"client slot {slot} was not staged")
+        self._staged(order)
         if not deltas and not self.has_baseline:
             raise ValueError("baseline not staged")
         if deltas and self.codec != "native":
@@ -825,12 +825,8 @@ class AggregationRound(RobustLaunches):
         order = list(range(len(weights64))) if order is None else list(order)
         if len(order) != len(weights64):
             raise ValueError("order and weights must have the same length")
-        slots = self._check_slots(order)
-        if not deltas and not self.has_baseline:
-            raise ValueError("baseline not staged")
-        if not deltas:
-            self._raw_only("launch_w64")
-        eng, lay = self.engine, self.layout
+        _, tf, ti, stream = self._staged_rows(order, baseline=not deltas, raw=None if deltas else "launch_w64")
+        eng = self.engine
         self.timings["stage_ms"] = (time.perf_counter() - self._t0) * 1e3
         self._k = len(order)
         w64 = torch.from_numpy(np.asarray([float(w) for w in weights64], dtype=np.float64)).to(eng.device)
@@ -838,19 +834,11 @@ class AggregationRound(RobustLaunches):
         if len(wi) != len(order):
             raise ValueError("weights_i64 must have one entry per client")
         wi = torch.from_numpy(wi).to(eng.device)
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
+        out_f, out_i = self._out_rows()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
-        n_i = lay.n_i64
-        _lib.call("plato_agg_fedavg_w64", _ptr(tf), _ptr(ti) if n_i else None, _ptr(w64), _ptr(wi), len(order),
-                  None if deltas else _ptr(self._base.f32), None if (deltas or not n_i) else _ptr(self._base.i64),
-                  _ptr(out_f), _ptr(out_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
+        _lib.call("plato_agg_fedavg_w64", *self._regions(tf, ti), _ptr(w64), _ptr(wi), len(order),
+                  *self._baseline(deltas), *self._regions(out_f, out_i), *self._sizes(stream))
         e1.record(stream)
         self._kernel_events = (e0, e1)
         self._fetch(stream, out_f, out_i, (tf, ti, w64, wi))
@@ -866,16 +854,54 @@ class AggregationRound(RobustLaunches):
         # keep device buffers alive until the copies finish
         self._out = (host_f, host_i, out_f, out_i, keep)
 
+    def _staged(self, slots: Sequence[int]) -> list[int]:
+        return staged_slots(self.capacity, self.staged, slots)
+
     def _check_slots(self, slots: Sequence[int]) -> list[int]:
-        slots = list(slots)
-        for slot in slots:
-            if not (0 <= slot < self.capacity and self.staged[slot]):
-                raise ValueError(f"client slot {slot} was not staged")
+        slots = self._staged(slots)
         if not slots:
             raise ValueError("no client slots")
         if self.codec != "native":
             raise ValueError("per-entry kernels take fp32 rows: run them on rnd.decoded() for coded payloads")
         return slots
+
+    def _staged_rows(self, slots: Sequence[int], *, baseline: bool = True, raw: str | None = None,
+                     tables: bool = True):
+        """What a launch over staged rows starts from: (slots, fp32 pointer table, int64 pointer table,
+        stream), the stream ordered behind the staged copies.  Refuses slots that are not staged or hold
+        codes, a missing baseline where the launch reads one (``baseline``), and a round of deltas where
+        ``raw`` names a launch that reads the weights.  ``tables=False`` (a launch that packs the row
+        pointers into a table of its own) uploads none and returns ``None`` for both."""
+        slots = self._check_slots(slots)
+        if baseline and not self.has_baseline:
+            raise ValueError("baseline not staged")
+        if raw is not None:
+            self._raw_only(raw)
+        tf, ti = self._row_tables(slots) if tables else (None, None)
+        stream = torch.cuda.current_stream(self.engine.device)
+        self.stager.fence(stream)
+        return slots, tf, ti, stream
+
+    def _row_tables(self, slots: Sequence[int]):
+        return self.engine._pointer_tables(np.asarray([self._pf[i] for i in slots], dtype=np.int64),
+                                           np.asarray([self._pi[i] for i in slots], dtype=np.int64))
+
+    def _out_rows(self):
+        lay, dev = self.layout, self.engine.device
+        return (torch.empty(lay.row_f32, dtype=torch.float32, device=dev),
+                torch.empty(lay.row_i64, dtype=torch.float32, device=dev))
+
+    def _regions(self, f32: torch.Tensor, i64: torch.Tensor):
+        """The C-ABI arguments of a two-region buffer: NULL for the int64 half of a layout without one."""
+        return f32.data_ptr(), (i64.data_ptr() if self.layout.n_i64 else None)
+
+    def _baseline(self, deltas: bool):
+        """The C-ABI arguments of the baseline; (NULL, NULL) where the rows already hold x - b (``deltas``:
+        the kernels then run in their deltas forms and read none)."""
+        return (None, None) if deltas else self._regions(self._base.f32, self._base.i64)
+
+    def _sizes(self, stream):  # the tail of a kernel call
+        return self.layout.n_f32, self.layout.n_i64, stream.cuda_stream
 
     def stage_reference(self, state_dict: Mapping[str, torch.Tensor]) -> DeviceArena:
         """Port's stored global model as a device arena, staged ahead of :meth:`model_similarities`
@@ -943,493 +969,6 @@ class AggregationRound(RobustLaunches):
         rnd._keep_decode = (keep, mv)
         self._decoded = rnd
         return rnd
-
-    def entry_stats(self, slots: Sequence[int], v: tuple | None = None, deltas: bool = False):
-        """Per (client, entry) fp64 sums over the staged slots (``plato_agg_entry_stats``).
-
-        ``d_i = x_i - baseline`` (``deltas=False``) or ``x_i``.  ``v`` is an
-        optional device vector ``(fp32 arena, fp32 values of the int64
-        entries)``, e.g. :meth:`launch_entrywise`'s ``device=True`` output.
-        Returns ``(dv [K, E] | None, dd [K, E], vv [E] | None)`` as float64
-        numpy arrays, entries in layout order.
-        """
-        slots = self._check_slots(slots)
-        deltas = deltas or self.deltas  # delta arenas: the rows are the deltas
-        if not deltas and not self.has_baseline:
-            raise ValueError("baseline not staged")
-        eng, lay = self.engine, self.layout
-        k, n_e = len(slots), len(lay.entries)
-        cf, ci = eng._chunks(lay, eng.STATS_CHUNK)
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        ncf, nci = int(cf.shape[0]), int(ci.shape[0])
-        ws = torch.empty((eng.lib.plato_agg_entry_stats_workspace(k, ncf + nci) + 7) // 8,
-                         dtype=torch.float64, device=eng.device)
-        out = torch.empty((2 * k + 1) * n_e, dtype=torch.float64, device=eng.device)
-        vf, vi = (None, None) if v is None else v
-        n_i = lay.n_i64
-        _lib.call("plato_agg_entry_stats", _ptr(tf), _ptr(ti) if n_i else None, k,
-                  None if deltas else _ptr(self._base.f32), None if (deltas or not n_i) else _ptr(self._base.i64),
-                  _ptr(vf), _ptr(vi) if (vf is not None and n_i) else None,
-                  _ptr(cf), ncf, _ptr(ci) if nci else None, nci, n_e, lay.n_f32, n_i, _ptr(ws), _ptr(out),
-                  _stream_handle(stream))
-        res = out.cpu().numpy().reshape(2 * k + 1, n_e)
-        if v is None:
-            return None, res[k:2 * k].copy(), None
-        return res[:k].copy(), res[k:2 * k].copy(), res[2 * k].copy()
-
-    def entry_norms(self, slots: Sequence[int]) -> np.ndarray:
-        """fp32 ``torch.linalg.norm`` of each (client, entry) delta in torch's CPU order.
-
-        Bit-equal to the reference's ``torch.linalg.norm(-delta)``
-        (fedatt_algorithm.py:39), by ``plato_agg_entry_norms_f32``; with
-        ``FedAvgEngine.norms_long_threshold`` set, the long fp32 entries go to
-        ``plato_agg_port_norms`` on a side stream instead (measured slower, off
-        by default).  Returns ``[E, K]`` float32 (entries in layout order,
-        clients in ``slots`` order).
-        """
-        slots = self._check_slots(slots)
-        self._raw_only("entry_norms")
-        if not self.has_baseline:
-            raise ValueError("baseline not staged")
-        eng, lay = self.engine, self.layout
-        k, n_e = len(slots), len(lay.entries)
-        ef, ei = eng._norm_tables(lay)  # one piece per entry, longest first
-        long_ids = [] if eng.norms_long_threshold is None else sorted(
-            (i for i, e in enumerate(lay.entries) if e.region == F32 and e.numel >= eng.norms_long_threshold),
-            key=lambda i: -lay.entries[i].numel)
-        if long_ids:
-            ef = eng._norm_tables_without(lay, tuple(long_ids))
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        out = torch.zeros(k * n_e, dtype=torch.float32, device=eng.device)
-        n_i = lay.n_i64
-        keep = ()
-        if long_ids:  # the long chains first, on their own stream
-            side = eng.side_stream()
-            side.wait_stream(stream)
-            base_f = _ptr(self._base.f32)
-            xs = [int(pf[j]) + 4 * lay.entries[e].offset for e in long_ids for j in range(k)]
-            bs = [base_f + 4 * lay.entries[e].offset for e in long_ids for j in range(k)]
-            lens = np.asarray([lay.entries[e].numel for e in long_ids for _ in range(k)], dtype=np.uint32)
-            n_max = int(lens.max())
-            tab = np.asarray(xs + xs + bs + bs, dtype=np.int64)  # int64 tables unused (one fp32 segment)
-            seg = np.zeros(1, dtype=[("flat", "<u8"), ("src", "<u8"), ("numel", "<u8"), ("region", "<u4"),
-                                     ("flags", "<u4")])
-            seg["numel"] = n_max
-            v = len(xs)
-            with torch.cuda.stream(side):
-                dt = torch.from_numpy(tab).to(eng.device)
-                dl = torch.from_numpy(lens.view(np.int32)).to(eng.device)
-                ds = torch.from_numpy(seg.view(np.int64).copy()).to(eng.device)
-                dn = torch.empty(v, dtype=torch.float32, device=eng.device)
-                p8, n8 = dt.data_ptr(), 8 * v
-                _lib.call("plato_agg_port_norms", p8, p8 + n8, p8 + 2 * n8, p8 + 3 * n8, v, dl.data_ptr(), ds.data_ptr(),
-                          1, n_max, lay.n_f32, 0, dn.data_ptr(), None, _stream_handle(side))
-                # scatter: vector (li, j) -> out[j * n_e + entry]
-                idx = torch.from_numpy(np.asarray([j * n_e + e for e in long_ids for j in range(k)],
-                                                  dtype=np.int64)).to(eng.device)
-                out.index_copy_(0, idx, dn)
-            keep = (dt, dl, ds, dn, idx)
-        nef, nei = int(ef.shape[0]), int(ei.shape[0])
-        if nef or nei:
-            with self._timed("entry_norms", stream):
-                _lib.call("plato_agg_entry_norms_f32", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(self._base.f32),
-                          _ptr(self._base.i64) if n_i else None, _ptr(ef) if nef else None, nef,
-                          _ptr(ei) if nei else None, nei, n_e, lay.n_f32, n_i, _ptr(out), _stream_handle(stream))
-        if long_ids:
-            stream.wait_stream(eng.side_stream())
-        res = np.ascontiguousarray(out.cpu().numpy().reshape(k, n_e).T)
-        self._resolve_timers()
-        del keep
-        return res
-
-    def launch_entrywise(self, weights: np.ndarray, order: Sequence[int] | None = None, scale: float = 1.0,
-                         noise: Mapping[str, torch.Tensor] | None = None, noise_scale: float = 0.0,
-                         add_base: bool = True, deltas: bool = False, device: bool = False):
-        """Weighted sum with a weight per (entry, client) (``plato_agg_fedavg_entrywise``).
-
-        ``weights`` is ``[E, K]`` (entries in layout order, clients in
-        ``order``), rounded to fp32 like torch's scalar multiply.  ``noise``
-        is a state_dict of fp32 tensors added as ``noise * noise_scale``.
-        ``device=True`` returns the device result ``(fp32 arena, int64
-        entries as fp32)`` instead of scheduling the D2H for :meth:`result`.
-        """
-        order = list(range(np.shape(weights)[1])) if order is None else list(order)
-        slots = self._check_slots(order)
-        if not deltas and not self.has_baseline:
-            raise ValueError("baseline not staged")
-        if self.deltas and not deltas:
-            if add_base:
-                self._raw_only("launch_entrywise(add_base=True)")
-            deltas = True  # the staged rows are the deltas the kernel would form
-        if deltas and add_base:
-            raise ValueError("add_base needs the baseline (deltas=False)")
-        eng, lay = self.engine, self.layout
-        k, n_e = len(slots), len(lay.entries)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
-        if w.shape != (n_e, k):
-            raise ValueError(f"weights must be [entries={n_e}, clients={k}], got {w.shape}")
-        cf, ci = eng._chunks(lay, eng.ENTRYWISE_CHUNK)
-        pf = np.asarray([self._pf[i] for i in slots], dtype=np.int64)
-        pi = np.asarray([self._pi[i] for i in slots], dtype=np.int64)
-        tf, ti = eng._pointer_tables(pf, pi)
-        dw = torch.from_numpy(w).to(eng.device)
-        nz = None
-        nst = None
-        if noise is not None:
-            nz = DeviceArena(lay, eng.device, i64_dtype=torch.float32)
-            lay.check_compatible(noise, "noise", "f32")
-            nst = eng._f32_stager(lay)
-            nst.put(noise, nz.f32, nz.i64)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        if nst is not None:
-            nst.fence(stream)
-        out_f = torch.empty(lay.row_f32, dtype=torch.float32, device=eng.device)
-        out_i = torch.empty(lay.row_i64, dtype=torch.float32, device=eng.device)
-        n_i = lay.n_i64
-        ncf, nci = int(cf.shape[0]), int(ci.shape[0])
-        _lib.call("plato_agg_fedavg_entrywise", _ptr(tf), _ptr(ti) if n_i else None, k, _ptr(dw), n_e,
-                  _ptr(cf), ncf, _ptr(ci) if nci else None, nci,
-                  None if deltas else _ptr(self._base.f32), None if (deltas or not n_i) else _ptr(self._base.i64),
-                  None if nz is None else _ptr(nz.f32), None if (nz is None or not n_i) else _ptr(nz.i64),
-                  float(scale), float(noise_scale), _lib.PLATO_AGG_ADD_BASE if add_base else 0,
-                  _ptr(out_f), _ptr(out_i) if n_i else None, lay.n_f32, n_i, _stream_handle(stream))
-        if device:
-            # inputs stay referenced by the caller's stream order; nothing to fetch
-            self._keep = (tf, ti, dw, nz)
-            return out_f, out_i
-        self._fetch(stream, out_f, out_i, (tf, ti, dw, nz))
-        return None
-
-    # ------------------------------------------- flattened-model reductions
-    def _flat_segments(self, order: Sequence[int], neg_div_after_first: bool) -> torch.Tensor:
-        """plato_agg_segment rows for the layout's entries in ``order`` (device, cached)."""
-        lay, eng = self.layout, self.engine
-        key = ("flat_segments", tuple(order), neg_div_after_first, str(eng.device))
-        hit = lay._cache.get(key)
-        if hit is None:
-            rows = np.zeros((len(order), 4), dtype=np.uint64)
-            flat = 0
-            for j, idx in enumerate(order):
-                e = lay.entries[idx]
-                flags = 1 if (neg_div_after_first and j > 0) else 0
-                region = 0 if e.region == F32 else 1
-                rows[j, 0], rows[j, 1], rows[j, 2] = flat, e.offset, e.numel
-                rows[j, 3] = np.uint64(region | (flags << 32))
-                flat += e.numel
-            hit = (torch.from_numpy(rows.view(np.int64).copy()).to(eng.device), flat)
-            lay._cache[key] = hit
-        return hit
-
-    def _flatten(self, mode: int, segs, n_segs: int, n_flat: int, src_f: Sequence[int], src_i: Sequence[int],
-                 base: tuple | None, lr: float, stream) -> tuple[torch.Tensor, int]:
-        """K flat vectors (rows of a [K, stride] buffer, stride 64-aligned) from device arenas."""
-        eng = self.engine
-        k = len(src_f)
-        stride = max(64, -(-n_flat // 64) * 64)
-        out = torch.empty((k, stride), dtype=torch.float32, device=eng.device)
-        ptrs = torch.from_numpy(np.asarray(list(src_f) + list(src_i) +
-                                           [out.data_ptr() + r * stride * 4 for r in range(k)],
-                                           dtype=np.int64)).to(eng.device)
-        base_f, base_i = (None, None) if base is None else base
-        _lib.call("plato_agg_flatten", mode, ptrs.data_ptr(), ptrs.data_ptr() + 8 * k, k, base_f, base_i,
-                  segs.data_ptr(), n_segs, n_flat, float(lr), ptrs.data_ptr() + 16 * k, _stream_handle(stream))
-        self._keep_flat = ptrs
-        return out, stride
-
-    def _fedadp_order(self):
-        lay = self.layout
-        order = fedadp_order(lay.keys())
-        if order and lay.entries[order[0]].region != F32:
-            raise ValueError("FedAdp: the first entry in name order is int64, so the reference flattens to "
-                             "float64 (np.append) and takes float64 dots; the device path reproduces the "
-                             "float32 case only")
-        return order
-
-    def fedadp_dots(self, grads: tuple[torch.Tensor, torch.Tensor], slots: Sequence[int], lr: float):
-        """FedAdp's float32 reductions of process_grad's flattened vectors, bit-exact.
-
-        ``grads`` is the device global gradient (fp32 arena, fp32 values of the
-        int64 entries), e.g. :meth:`launch_entrywise` with ``device=True``.
-        Returns ``(inner[K], g_sq, l_sq[K])`` as numpy float32: ``np.inner(g,
-        loc_k)``, ``g.dot(g)``, ``loc_k.dot(loc_k)`` exactly as numpy's OpenBLAS
-        forms them (examples/server_aggregation/fedadp/fedadp_server.py:91-99).
-        The global gradient is flattened once (``plato_agg_flatten``, RAW); the
-        clients' loc_k are gathered from their staged arenas inside
-        ``plato_agg_fedadp_dots``, which runs the sdot chains with no flattened
-        copies of the K deltas.
-        """
-        slots = self._check_slots(slots)
-        if not self.has_baseline:
-            raise ValueError("baseline not staged")
-        eng, lay = self.engine, self.layout
-        order = self._fedadp_order()
-        segs, n_flat = self._flat_segments(order, True)
-        # plato_agg_fedadp_dots' limits (csrc/fedadp.hip run_fedadp); beyond them the round-2 path
-        if (len(order) >= self.FEDADP_MAX_SEGS or n_flat >= 1 << 30 or lay.n_f32 >= 1 << 30
-                or lay.n_i64 >= 1 << 30 or len(slots) > 65535
-                or self.fedadp_boundary_rows(len(order), lay.n_i64) >= self.FEDADP_MAX_BND):
-            return self.fedadp_dots_flat(grads, slots, lr)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        g_flat, _ = self._flatten(_lib.PLATO_AGG_FLAT_RAW, segs, len(order), n_flat, [grads[0].data_ptr()],
-                                  [grads[1].data_ptr()], None, lr, stream)
-        k = len(slots)
-        ptrs = torch.from_numpy(np.asarray([self._pf[i] for i in slots] + [self._pi[i] for i in slots],
-                                           dtype=np.int64)).to(eng.device)
-        xy = torch.empty(k + 1, dtype=torch.float32, device=eng.device)
-        yy = torch.empty(k + 1, dtype=torch.float32, device=eng.device)
-        # The workspace's layout-only tables (descriptors, boundary rows and their sources) depend on the
-        # segment map alone (`segs`, cached on the layout): the engine keeps its last workspace, and its next
-        # round of the same layout and K skips building them (PLATO_AGG_FEDADP_TABLES_READY).  Per engine,
-        # not per layout: an engine runs one round at a time, while several engines (a client-split round's
-        # devices, repeated devices in tests) may reduce the same layout concurrently.
-        ws_key = (id(lay), lay.signature, tuple(order), k, segs.data_ptr())
-        held = getattr(eng, "_fedadp_ws", None)
-        if held is not None and held[0] == ws_key and held[1] is lay:
-            ws, flags = held[2], _lib.PLATO_AGG_FEDADP_TABLES_READY
-        else:
-            eng._fedadp_ws = None  # one workspace per engine (K varies between async rounds)
-            ws = torch.empty(-(-_lib.lib().plato_agg_fedadp_dots_workspace(k, 1, lay.n_i64, n_flat, len(order)) // 4),
-                             dtype=torch.float32, device=eng.device)
-            flags = 0
-        n_i = lay.n_i64
-        with self._timed("fedadp_dots", stream):
-            # delta arenas: a null baseline selects the kernel that streams none (same values, same order)
-            base_f = None if self.deltas else _ptr(self._base.f32)
-            base_i = None if (self.deltas or not n_i) else _ptr(self._base.i64)
-            _lib.call("plato_agg_fedadp_dots_ex", g_flat.data_ptr(), ptrs.data_ptr(), ptrs.data_ptr() + 8 * k, k,
-                      base_f, base_i, segs.data_ptr(), len(order), n_flat,
-                      lay.n_f32, n_i, float(lr), 1, ws.data_ptr(), xy.data_ptr(), yy.data_ptr(), _stream_handle(stream),
-                      flags)
-        xy_h, yy_h = xy.cpu().numpy(), yy.cpu().numpy()  # stream-ordered D2H (syncs this stream)
-        eng._fedadp_ws = (ws_key, lay, ws)  # its tables are built (this stream has passed the call)
-        self._resolve_timers()
-        self._keep_flat = (g_flat, ptrs, ws)
-        return xy_h[:k], xy_h[k], yy_h[:k]
-
-    def fedadp_dots_flat(self, grads: tuple[torch.Tensor, torch.Tensor], slots: Sequence[int], lr: float,
-                         batch_bytes: float = 32e9):
-        """The same dots through materialised flat vectors (``plato_agg_flatten`` + ``plato_agg_sdot_shared``).
-
-        The round-2 path, kept as an independent device cross-check of
-        :meth:`fedadp_dots` (tests), for the before/after timing
-        (scripts/bench_variant_paths.py), and for models beyond the fused
-        kernel's limits (:meth:`fedadp_dots` falls back here).  On delta arenas
-        the rows are flattened against a zero arena: x - 0 = x for the fp32
-        deltas, and the int64 deltas are the exact int64 differences either way.
-        """
-        slots = self._check_slots(slots)
-        if not self.has_baseline:
-            raise ValueError("baseline not staged")
-        eng, lay = self.engine, self.layout
-        order = self._fedadp_order()
-        segs, n_flat = self._flat_segments(order, True)
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        g_flat, stride = self._flatten(_lib.PLATO_AGG_FLAT_RAW, segs, len(order), n_flat, [grads[0].data_ptr()],
-                                       [grads[1].data_ptr()], None, lr, stream)
-        k = len(slots)
-        # rows 0..k-1: g.loc_k and loc_k.loc_k; row k: g.g (the global gradient's squared norm),
-        # which the last batch's launch forms alongside (with_xx)
-        xy = torch.empty(k + 1, dtype=torch.float32, device=eng.device)
-        yy = torch.empty(k + 1, dtype=torch.float32, device=eng.device)
-        per = max(1, int(batch_bytes // (stride * 4)))
-        ws = torch.empty(_lib.lib().plato_agg_sdot_shared_workspace(min(k, per), 1) // 4, dtype=torch.float32,
-                         device=eng.device)
-        zero = None
-        if self.deltas:  # the rows already hold x - b
-            zero = DeviceArena(lay, eng.device)
-            zero.f32.zero_()
-            zero.i64.zero_()
-            base = (_ptr(zero.f32), _ptr(zero.i64))
-        else:
-            base = (_ptr(self._base.f32), _ptr(self._base.i64))
-        keep = [zero]
-        for s0 in range(0, k, per):
-            part = slots[s0:s0 + per]
-            locs, _ = self._flatten(_lib.PLATO_AGG_FLAT_DELTA, segs, len(order), n_flat,
-                                    [self._pf[i] for i in part], [self._pi[i] for i in part], base, lr, stream)
-            last = s0 + per >= k
-            ys_h = [locs.data_ptr() + r * stride * 4 for r in range(len(part))]
-            ys = torch.from_numpy(np.asarray(ys_h, dtype=np.int64)).to(eng.device)
-            _lib.call("plato_agg_sdot_shared", g_flat.data_ptr(), ys.data_ptr(), len(ys_h), n_flat, int(last),
-                      ws.data_ptr(), xy.data_ptr() + 4 * s0, yy.data_ptr() + 4 * s0, _stream_handle(stream))
-            keep.append((locs, ys))
-            if s0 + per < k:
-                stream.synchronize()  # bound the flat buffers to one batch
-                keep = [zero]
-        stream.synchronize()
-        xy_h, yy_h = xy.cpu().numpy(), yy.cpu().numpy()
-        inner, g_sq, l_sq = xy_h[:k], xy_h[k], yy_h[:k]
-        return inner, g_sq, l_sq
-
-    def np_sumsq(self, slots: Sequence[int]) -> np.ndarray:
-        """numpy's float32 ``np.sum(np.square(x - b))`` of every fp32 entry, per client, bit-exact.
-
-        Polaris' per-layer squared deltas (examples/client_selection/polaris/
-        polaris_server.py:78-81) in numpy's own order (``plato_agg_np_sumsq``).
-        Returns ``[K, E]`` float32 (entries in layout order; int64 entries 0).
-        """
-        slots = self._check_slots(slots)
-        if not self.has_baseline:
-            raise ValueError("baseline not staged")
-        eng, lay = self.engine, self.layout
-        key = ("np_sumsq_pieces", str(eng.device))
-        hit = lay._cache.get(key)
-        if hit is None:
-            rows, first, n_chunks = [], [], 0
-            for idx, e in enumerate(lay.entries):
-                if e.region == F32 and e.numel:
-                    rows.append((idx, e.offset, e.offset + e.numel, 0))
-                    first.append(n_chunks)
-                    n_chunks += -(-e.numel // 8192)
-            pieces = np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
-            hit = (torch.from_numpy(pieces.view(np.int32).copy()).to(eng.device),
-                   torch.from_numpy(np.asarray(first, dtype=np.uint32).view(np.int32)).to(eng.device),
-                   pieces[:, 0].astype(np.int64), n_chunks)
-            lay._cache[key] = hit
-        pieces, first, entry_of, n_chunks = hit
-        k, n_p = len(slots), int(entry_of.size)
-        out = np.zeros((k, len(lay.entries)), dtype=np.float32)
-        if n_p == 0:
-            return out
-        stream = torch.cuda.current_stream(eng.device)
-        self.stager.fence(stream)
-        tf = torch.from_numpy(np.asarray([self._pf[i] for i in slots], dtype=np.int64)).to(eng.device)
-        ws = torch.empty(max(1, eng.lib.plato_agg_np_sumsq_workspace(k, n_chunks) // 4), dtype=torch.float32,
-                         device=eng.device)
-        dev_out = torch.empty((k, n_p), dtype=torch.float32, device=eng.device)
-        with self._timed("np_sumsq", stream):
-            # delta arenas: a null baseline selects the kernels that load none (the rows hold x - b)
-            _lib.call("plato_agg_np_sumsq", tf.data_ptr(), k, None if self.deltas else _ptr(self._base.f32),
-                      pieces.data_ptr(),
-                      first.data_ptr(), n_p, n_chunks, ws.data_ptr(), dev_out.data_ptr(), _stream_handle(stream))
-        out[:, entry_of] = dev_out.cpu().numpy()
-        self._resolve_timers()
-        return out
-
-    PORT_NORMS_MAX_SEGS = 2048  # csrc/port.hip kMaxSegs
-    FEDADP_MAX_SEGS = 1 << 22   # csrc/fedadp.hip run_fedadp
-    FEDADP_MAX_BND = 1 << 22    # boundary-table rows (32-bit byte offsets of 1 KiB rows)
-
-    @staticmethod
-    def fedadp_boundary_rows(n_segs: int, n_i64: int) -> int:
-        """csrc/fedadp.hip adp_max_bnd: boundary-table rows the kernel reserves per pair."""
-        return 2 * (n_segs + n_i64 // 256 + 1)
-
-    def model_similarities(self, reference: Mapping[str, torch.Tensor], slots: Sequence[int],
-                           eps: float = 1e-8, threads: int | None = None, flat_norms: bool = False) -> list[np.float32]:
-        """Port's cosine similarity of each client delta with ``baseline - reference``, bit-exact.
-
-        ``F.cosine_similarity(current - previous, delta, dim=0)`` over the
-        models flattened by ``torch.cat`` in state_dict order
-        (examples/async/port/port_server.py:24-52), computed on the device in
-        the order x86-64 PyTorch 2.10 uses on ``threads`` CPU threads (default
-        ``torch.get_num_threads()``: what the reference's call would use in this
-        process).  ``plato_agg_port_norms`` gathers ``current - previous`` and
-        every client delta straight from the staged arenas for the vector norms
-        (serial-chain bound) and stores the flattened vectors as it goes; the
-        cascade cosine sums (``plato_agg_torch_cosine_sum``) then read those.
-        ``flat_norms=True`` runs the round-2 path instead — ``plato_agg_flatten``,
-        then ``plato_agg_entry_norms_f32`` over the flat rows — kept as a device
-        cross-check.
-        Returned as fp32 like the reference's 0-dim tensor.
-        """
-        if not self.has_baseline:
-            raise ValueError("baseline not staged")
-        slots = list(slots)
-        for slot in slots:
-            if not (0 <= slot < self.capacity and self.staged[slot]):
-                raise ValueError(f"client slot {slot} was not staged")
-        if not slots:
-            return []
-        slots = self._check_slots(slots)
-        threads = torch.get_num_threads() if threads is None else int(threads)
-        eng = self.engine
-        lay = self.layout
-        stream = torch.cuda.current_stream(eng.device)
-        if isinstance(reference, DeviceArena):  # staged ahead by stage_reference
-            if reference.layout is not lay:
-                raise ValueError("reference arena was staged for another round / layout")
-            prev = reference
-        else:
-            prev = self._stage_model(reference, "reference model", stream)
-        self.stager.fence(stream)
-        segs, n_flat = self._flat_segments(list(range(len(lay.entries))), False)
-        n_segs = len(lay.entries)
-        base = (_ptr(self._base.f32), _ptr(self._base.i64))
-        stride = max(64, -(-n_flat // 64) * 64)
-        k = len(slots)
-        h = _stream_handle(stream)
-        # plato_agg_port_norms keeps the segment map in LDS (<= PORT_NORMS_MAX_SEGS entries) and takes
-        # n_flat < 2^31, n_f32 < 2^30: larger models take the flatten + entry_norms path (same bits)
-        if n_segs > self.PORT_NORMS_MAX_SEGS or n_flat >= 1 << 31 or lay.n_f32 >= 1 << 30:
-            flat_norms = True
-        norms = torch.empty(k + 1, dtype=torch.float32, device=eng.device)
-        ws = torch.empty(max(1, eng.lib.plato_agg_torch_cosine_workspace(k, threads) // 4), dtype=torch.float32,
-                         device=eng.device)
-        out = torch.empty(k, dtype=torch.float32, device=eng.device)
-        if flat_norms:  # the round-2 path: flattened vectors, norms and sums over them
-            cur, _ = self._flatten(_lib.PLATO_AGG_FLAT_CAST_DIFF, segs, n_segs, n_flat, [base[0]], [base[1]],
-                                   (_ptr(prev.f32), _ptr(prev.i64)), 0.0, stream)
-            # (delta arenas: the rows minus a zero arena, x - 0 = x, int64 differences cast once as before)
-            zero = None
-            if self.deltas:
-                zero = DeviceArena(lay, eng.device)
-                zero.f32.zero_()
-                zero.i64.zero_()
-            sub = (_ptr(zero.f32), _ptr(zero.i64)) if self.deltas else base
-            deltas, _ = self._flatten(_lib.PLATO_AGG_FLAT_DELTA, segs, n_segs, n_flat, [self._pf[i] for i in slots],
-                                      [self._pi[i] for i in slots], sub, 0.0, stream)
-            rows = [cur.data_ptr()] + [deltas.data_ptr() + r * stride * 4 for r in range(k)]
-            tab = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(eng.device)
-            chunk = torch.from_numpy(np.asarray([[0, 0, n_flat, 0]], dtype=np.uint32).view(np.int32)).to(eng.device)
-            # the rows are `stride` long (the padding past n_flat is read, never summed): declaring that length keeps
-            # the one n_flat-long piece off the kernel's partial-last-float4 fallback (a per-wave path ~1.5x slower)
-            _lib.call("plato_agg_entry_norms_f32", tab.data_ptr(), None, k + 1, None, None, chunk.data_ptr(), 1, None,
-                      0, 1, stride, 0, norms.data_ptr(), h)
-            _lib.call("plato_agg_torch_cosine_sum", cur.data_ptr(), tab.data_ptr() + 8, k, n_flat, norms.data_ptr(),
-                      norms.data_ptr() + 4, float(eps), threads, ws.data_ptr(), out.data_ptr(), h)
-            keep = (cur, deltas, tab, chunk, zero)
-        else:  # norms straight from the arenas; the same kernel stores the flattened vectors for the sums
-            flat = torch.empty((k + 1, stride), dtype=torch.float32, device=eng.device)
-            vec = np.asarray([base[0]] + [self._pf[i] for i in slots]
-                             + [base[1] or 0] + [self._pi[i] or 0 for i in slots]
-                             # client vectors subtract the baseline, or nothing on delta arenas (null)
-                             + [_ptr(prev.f32)] + [0 if self.deltas else base[0]] * k
-                             + [_ptr(prev.i64) or 0] + [0 if self.deltas else (base[1] or 0)] * k
-                             + [flat.data_ptr() + r * stride * 4 for r in range(k + 1)], dtype=np.int64)
-            vt = torch.from_numpy(vec).to(eng.device)
-            v8, n1 = vt.data_ptr(), 8 * (k + 1)
-            scaled = torch.empty(stride, dtype=torch.float32, device=eng.device)
-            args = (v8, v8 + n1, v8 + 2 * n1, v8 + 3 * n1, k + 1, None, segs.data_ptr(), n_segs, n_flat, lay.n_f32,
-                    _lib.PLATO_AGG_PORT_CAST_FIRST, norms.data_ptr(), v8 + 4 * n1, h)
-            with self._timed("port_norms", stream):
-                if eng.port_variant is None:
-                    _lib.call("plato_agg_port_norms", *args)
-                else:
-                    _lib.tune_call("plato_agg_tune_port_norms", eng.port_variant, *args)
-            # current - previous over its norm once (not once per client), then the K cascade sums
-            with self._timed("port_cosine", stream):
-                _lib.call("plato_agg_scale_by_norm", flat.data_ptr(), n_flat, norms.data_ptr(), float(eps),
-                          scaled.data_ptr(), h)
-                _lib.call("plato_agg_torch_cosine_sum_scaled", scaled.data_ptr(), v8 + 4 * n1 + 8, k, n_flat,
-                          norms.data_ptr() + 4, float(eps), threads, ws.data_ptr(), out.data_ptr(), h)
-            keep = (vt, flat, scaled)
-        stream.synchronize()
-        self._resolve_timers()
-        del keep
-        self.last_norms = norms.cpu().numpy()
-        return [np.float32(v) for v in out.cpu().numpy()]
 
     def ready(self) -> bool:
         return self.event is not None and self.event.query()

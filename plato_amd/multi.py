@@ -51,14 +51,11 @@ from . import _lib
 from .arena import CODECS, ArenaLayout, payload_codec, same_f32_bits
 from .arrivals import Adopt, ArrivalTable, adopt_or_put, adopt_rule
 from .distributed import BucketPlan, EntryPlan
-from .engine import FedAvgEngine, fp32_weights, require_device
+from .engine import FedAvgEngine, _ptr, fp32_weights, require_device, staged_slots
+from .reductions import entrywise_weights
 from .staging import HostPacker, PinnedRing, ResultPool, arena_source, baseline_key
 
 MULTI_CODECS = ("native", "bf16")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class _Shard:
@@ -533,9 +530,7 @@ class MultiRound:
         order = list(range(len(weights))) if order is None else list(order)
         if len(order) != len(weights):
             raise ValueError("order and weights must have the same length")
-        for slot in order:
-            if not (0 <= slot < self.capacity and self.staged[slot]):
-                raise ValueError(f"client slot {slot} was not staged")
+        staged_slots(self.capacity, self.staged, order)
         if not deltas and not self.has_baseline:
             raise ValueError("baseline not staged")
         if deltas and self.codec != "native":
@@ -844,14 +839,10 @@ class ClientRound(MultiRound):
         rows_are_deltas = self.deltas  # the kernel's deltas form: no baseline read
         eng, lay = self.engine, self.layout
         n_e = len(lay.entries)
-        order = list(range(np.asarray(weights).shape[1])) if order is None else list(order)
-        for j in order:
-            if not (0 <= j < self.capacity and self.staged[j]):
-                raise ValueError(f"client slot {j} was not staged")
+        order = staged_slots(self.capacity, self.staged,
+                             range(np.asarray(weights).shape[1]) if order is None else order)
         k = len(order)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
-        if w.shape != (n_e, k):
-            raise ValueError(f"weights must be [entries={n_e}, clients={k}], got {w.shape}")
+        w = entrywise_weights(weights, n_e, k)
         tables = self._bucket_chunks()
         outs, keep = [], []
         for s, (cf, ci) in zip(eng._shards, tables):

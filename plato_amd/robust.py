@@ -25,14 +25,14 @@ class RobustLaunches:
     """``launch_*`` of the robust aggregators (mixin of ``AggregationRound``)."""
 
     def _robust_rows(self, what: str, order: Sequence[int] | None, whole_model: bool = True, check=None):
-        """(slots, fp32 pointer table, int64 pointer table, stream) of a robust launch, the stream
-        ordered behind the staged copies.  Every refusal comes before any GPU work; ``whole_model``
-        adds those of the launches that sum over the flattened model, ``check(K)`` the caller's own."""
+        """``_staged_rows`` of a robust launch (weights, no baseline; default: every staged slot) with
+        the robust refusals, all before any kernel; ``whole_model`` adds those of the launches that sum
+        over the flattened model, ``check(K)`` the caller's own."""
         if self.codec != "native":
             raise ValueError(f"robust aggregation takes native payloads; this round holds {self.codec} codes")
         self._raw_only(what)
-        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else list(order)
-        slots = self._check_slots(order)
+        order = [i for i in range(self.capacity) if self.staged[i]] if order is None else order
+        slots, tf, ti, stream = self._staged_rows(order, baseline=False)
         if whole_model:
             if len(slots) > _lib.PLATO_AGG_ROBUST_MAX_K:
                 raise ValueError(f"robust aggregation takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, "
@@ -41,9 +41,6 @@ class RobustLaunches:
                 raise ValueError(f"{what} sums over the whole fp32 region: the arena must have no alignment padding")
         if check is not None:
             check(len(slots))
-        tf, ti = self._row_tables(slots)
-        stream = torch.cuda.current_stream(self.engine.device)
-        self.stager.fence(stream)
         return slots, tf, ti, stream
 
     def _launch_rows(self, what: str, order, body, whole_model: bool = True, check=None) -> None:
@@ -60,22 +57,6 @@ class RobustLaunches:
         self._kernel_events = (e0, e1)
         self._robust = True
         self._fetch(stream, out_f, out_i, (tf, ti, *keep))
-
-    def _row_tables(self, slots: Sequence[int]):
-        return self.engine._pointer_tables(np.asarray([self._pf[i] for i in slots], dtype=np.int64),
-                                           np.asarray([self._pi[i] for i in slots], dtype=np.int64))
-
-    def _out_rows(self):
-        lay, dev = self.layout, self.engine.device
-        return (torch.empty(lay.row_f32, dtype=torch.float32, device=dev),
-                torch.empty(lay.row_i64, dtype=torch.float32, device=dev))
-
-    def _regions(self, f32: torch.Tensor, i64: torch.Tensor):
-        """The C-ABI arguments of a two-region buffer: NULL for the int64 half of a layout without one."""
-        return f32.data_ptr(), (i64.data_ptr() if self.layout.n_i64 else None)
-
-    def _sizes(self, stream):  # the tail of a kernel call
-        return self.layout.n_f32, self.layout.n_i64, stream.cuda_stream
 
     def _robust_columns(self, mode: str, tf, ti, k: int, trim: int, out_f, out_i, stream) -> None:
         with self._timed("robust_" + mode, stream):

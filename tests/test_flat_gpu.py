@@ -234,14 +234,28 @@ def test_np_sumsq_equals_numpy_order():
             assert got[c, e_i].tobytes() == R.np_sum(np.square(d)).tobytes()
 
 
-@pytest.mark.parametrize("mode", [_lib.PLATO_AGG_FLAT_DELTA, _lib.PLATO_AGG_FLAT_CAST_DIFF, _lib.PLATO_AGG_FLAT_RAW])
+# planted in the deltas of the null-baseline cases: (entry, positions, values), the same in every client; the
+# 70,001-element entry takes them at a workgroup's first and last positions (2,048 per workgroup) and in its tail
+_F32_SPECIALS = np.array([-0.0, 0.0, 1e-45, np.finfo(np.float32).max, np.inf, -np.inf, np.nan], dtype=np.float32)
+_PLANTED = [("d", [0, 2047, 2048, 34999, 69631, 69632, 70000], _F32_SPECIALS),
+            ("a", [0, 1, 2, 3, 4], _F32_SPECIALS[[0, 2, 3, 5, 6]]),
+            ("n1", [0, 1, 2], np.array([np.iinfo(np.int64).min, np.iinfo(np.int64).max, -1], dtype=np.int64)),
+            ("n0", [0], np.array([np.iinfo(np.int64).min], dtype=np.int64))]
+
+
+@pytest.mark.parametrize("mode,null_base", [
+    pytest.param(_lib.PLATO_AGG_FLAT_DELTA, False, id="0"), pytest.param(_lib.PLATO_AGG_FLAT_CAST_DIFF, False, id="1"),
+    pytest.param(_lib.PLATO_AGG_FLAT_RAW, False, id="2"), pytest.param(_lib.PLATO_AGG_FLAT_DELTA, True, id="0-null_base")])
 @pytest.mark.parametrize("k", [1, 8, 11])
-def test_flatten_modes_match_numpy(mode, k):
+@np.errstate(over="ignore")  # FLT_MAX / lr
+def test_flatten_modes_match_numpy(mode, null_base, k):
     """plato_agg_flatten: segments in a permuted order (fp32 and int64 entries, ragged sizes, every
     source/flat alignment), -1/lr on some segments, client groups of 8 with a ragged last group
     (the baseline is read once per group): equal to the numpy restatement of torch.cat / FedAdp's
-    process_grad element by element."""
-    rng = np.random.default_rng(100 * mode + k)
+    process_grad element by element.  ``null_base``: DELTA with d_base_f32 = d_base_i64 = NULL over sources
+    that hold deltas (delta arenas), signed zeros, a subnormal, FLT_MAX, infinities, a NaN and the int64
+    extremes among them; numpy subtracts a float32 +0 (fp32) and casts the int64 values as they are."""
+    rng = np.random.default_rng(100 * mode + k + 1000 * null_base)
     sizes = [("a", 5, "f32"), ("n0", 1, "i64"), ("b", 4099, "f32"), ("c", 37, "f32"), ("n1", 3, "i64"),
              ("d", 70001, "f32"), ("e", 2, "f32")]
     off = {"f32": 0, "i64": 0}
@@ -256,6 +270,13 @@ def test_flatten_modes_match_numpy(mode, k):
     xf = [bf + rng.standard_normal(n_f).astype(np.float32) * 0.1 for _ in range(k)]
     xi = [bi + rng.integers(-5, 5, n_i) for _ in range(k)]
     xi_raw = [rng.standard_normal(n_i).astype(np.float32) for _ in range(k)]  # RAW: fp32 values
+    if null_base:  # the sources are the deltas themselves
+        xf = [x - bf for x in xf]
+        xi = [x - bi for x in xi]
+        where = {name: so for name, _, _, so in ents}
+        for name, pos, vals in _PLANTED:
+            for x in (xf if vals.dtype == np.float32 else xi):
+                x[where[name] + np.asarray(pos)] = vals
     order = list(rng.permutation(len(ents)))
     rows, flat, want = [], 0, [[] for _ in range(k)]
     for j, idx in enumerate(order):
@@ -266,7 +287,10 @@ def test_flatten_modes_match_numpy(mode, k):
         for c in range(k):
             if reg == "f32":
                 x = xf[c][so:so + n]
-                v = x if mode == _lib.PLATO_AGG_FLAT_RAW else np.subtract(x, bf[so:so + n], dtype=np.float32)
+                if mode == _lib.PLATO_AGG_FLAT_RAW:
+                    v = x
+                else:
+                    v = np.subtract(x, np.float32(0) if null_base else bf[so:so + n], dtype=np.float32)
                 if neg:
                     v = np.divide(-v, lr, dtype=np.float32)
             elif mode == _lib.PLATO_AGG_FLAT_RAW:
@@ -279,9 +303,22 @@ def test_flatten_modes_match_numpy(mode, k):
                 if neg:
                     v = np.divide(-v, lr, dtype=np.float32)
             else:
-                d = (xi[c][so:so + n] - bi[so:so + n]).astype(np.int64)
+                d = xi[c][so:so + n] if null_base else (xi[c][so:so + n] - bi[so:so + n]).astype(np.int64)
                 v = np.divide((-d).astype(np.float32), lr, dtype=np.float32) if neg else d.astype(np.float32)
             want[c].append(np.asarray(v, dtype=np.float32))
+    if null_base:  # the expectation still holds every planted value where it was put (CPU only)
+        at = {ents[idx][0]: (row[0], bool(row[3] >> 32)) for idx, row in zip(order, rows)}
+        for name, pos, vals in _PLANTED:
+            fo, neg = at[name]
+            if vals.dtype == np.float32:  # the planted bits themselves, or their -v / lr: each still what it was
+                exp = np.divide(-vals, lr, dtype=np.float32) if neg else vals
+                assert (np.isnan(exp) == np.isnan(vals)).all() and ((exp == 0) == (vals == 0)).all()
+                assert (np.signbit(exp) == (np.signbit(vals) ^ neg)).all()
+            else:  # +-2^63 and -1, or over lr after the wrapping negation
+                exp = np.divide((-vals).astype(np.float32), lr, dtype=np.float32) if neg else vals.astype(np.float32)
+                assert (np.abs(exp) >= 1).all()
+            for c in range(k):
+                assert np.concatenate(want[c])[fo + np.asarray(pos)].tobytes() == exp.tobytes(), (name, c)
     segs = torch.from_numpy(np.asarray(rows, dtype=np.uint64).view(np.int64)).to(DEV)
     stride = -(-flat // 64) * 64
     out = torch.full((k, stride), float("nan"), device=DEV)
@@ -290,9 +327,19 @@ def test_flatten_modes_match_numpy(mode, k):
     ptrs = torch.tensor([t.data_ptr() for t in src_f] + [t.data_ptr() for t in src_i] +
                         [out.data_ptr() + r * stride * 4 for r in range(k)], dtype=torch.int64, device=DEV)
     b_f, b_i = torch.from_numpy(bf).to(DEV), torch.from_numpy(bi).to(DEV)
-    _lib.call("plato_agg_flatten", mode, ptrs.data_ptr(), ptrs.data_ptr() + 8 * k, k, b_f.data_ptr(), b_i.data_ptr(),
+    _lib.call("plato_agg_flatten", mode, ptrs.data_ptr(), ptrs.data_ptr() + 8 * k, k,
+              None if null_base else b_f.data_ptr(), None if null_base else b_i.data_ptr(),
               segs.data_ptr(), len(rows), flat, float(lr), ptrs.data_ptr() + 16 * k,
               torch.cuda.current_stream().cuda_stream)
     got = out.cpu().numpy()[:, :flat]
     for c in range(k):
         assert got[c].tobytes() == np.concatenate(want[c]).tobytes(), c
+
+
+def test_flatten_refuses_a_missing_baseline():
+    """Before any launch: CAST_DIFF without a baseline, and DELTA with one of the two regions only."""
+    a = 1 << 12  # any aligned non-null address: nothing is dereferenced on these paths
+    flatten = _lib.lib().plato_agg_flatten
+    assert flatten(_lib.PLATO_AGG_FLAT_CAST_DIFF, a, a, 1, None, None, a, 1, 8, 1.0, a, None) == _lib.PLATO_AGG_EINVAL
+    for base in ((a, None), (None, a)):
+        assert flatten(_lib.PLATO_AGG_FLAT_DELTA, a, a, 1, *base, a, 1, 8, 1.0, a, None) == _lib.PLATO_AGG_EINVAL

@@ -723,7 +723,7 @@ def test_fedadp_dots_many_entries_match_oracle(engine, n_entries, deltas):
     """More entries than the round-3 kernel's 2,048-entry segment map: every boundary group goes through
     the boundary table; the dots equal numpy's sdot order (oracle) and the flatten + sdot path bit for bit.
     ``delta_arenas``: the clients staged as deltas (FedAdp's servers' default), where the fallback to the
-    flat path for models past the fused kernel's limits flattens the delta rows against a zero arena."""
+    flat path for models past the fused kernel's limits flattens the delta rows with a null baseline."""
     from oracle import fedavg_oracle as FO
     from oracle import reductions as R
 
