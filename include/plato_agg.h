@@ -77,6 +77,11 @@
  *                                 413-423, :432-433) and the scaled candidates and
  *                                 their torch.sum (:428-441); torch.mean (:408) is
  *                                 plato_agg_mean_rows
+ *   plato_agg_detect_means,    <- the detector example's FLDetector defence
+ *   plato_agg_rows_dots,          (examples/detector/detectors.py:67-106, 310-418):
+ *   plato_agg_lbfgs_predict,      the means and record rows of a round, the Gram
+ *   plato_agg_delta_sqdist        matrices of lbfgs(), its prediction and the
+ *                                 clients' distances to it
  */
 #ifndef PLATO_AGG_H
 #define PLATO_AGG_H
@@ -805,6 +810,92 @@ int plato_agg_column_std(const float* const* d_x_f32, const int64_t* const* d_x_
 int plato_agg_add_scaled_rows(float* const* d_x_f32, int64_t* const* d_x_i64, int m, float s,
                               const float* d_v_f32, const float* d_v_i64_as_f32,
                               size_t n_f32, size_t n_i64, hipStream_t stream);
+
+/*
+ * FLDetector (examples/detector/detectors.py:67-106 lbfgs, 310-418 fl_detector,
+ * "FLDetector" of server.detector_type): the mean update of a round is predicted
+ * from a record of N global-weight differences S and N mean-update differences Y by
+ * the L-BFGS compact form, and every client is scored by the distance of its update
+ * to the prediction.  The 2N x 2N system and the clustering of the K scores are the
+ * host's (plato_amd/detectors.py); everything that streams the model is here.
+ *
+ * Notation.  D = n_f32 + n_i64.  A flat row is D contiguous fp32 values in arena
+ * order: the fp32 region, then the int64 region as fp32; it is 4-byte aligned.
+ * c_k[e] is client k's weight (x in the fp32 region, (float)x in the int64 region),
+ * d_k[e] its delta as plato_agg_compute_deltas forms it, promoted to fp32: the fp32
+ * subtraction x - b in the fp32 region, the wrapping int64 subtraction rounded once
+ * to fp32 in the int64 region.  b is the baseline arena, bf[e] = b[e] or (float)b[e].
+ *
+ * plato_agg_detect_means  <- torch.mean(flattened_deltas_attacked, dim=0),
+ *                            torch.mean(weights_attacked - last_weights, dim=0),
+ *                            flattened_baseline_weights - last_weights,
+ *                            mean - last_gradients
+ *   One pass over the K client rows, b, last_w and last_g writes the four flat rows
+ *   g, v, s_new, y_new, and the baseline as a flat row (the next round's last_w):
+ *     g[e]     = (float)(sum_k (double)d_k[e] / (double)K)
+ *     v[e]     = (float)(sum_k (double)fp32(c_k[e] - last_w[e]) / (double)K)
+ *     s_new[e] = fp32(bf[e] - last_w[e])
+ *     y_new[e] = fp32(g[e] - last_g[e])
+ *     b_flat[e] = bf[e]
+ *   The sums start at +0 and run over k in table order in float64, each addition
+ *   and the division separately rounded; fp32(.) is one fp32 subtraction.
+ *
+ * plato_agg_rows_dots  <- torch.matmul(global_weights, gradients.T) and its kin
+ *   d_out[r * m + j] = sum over e of rows[r][e] * vecs[j][e] for R flat rows and m
+ *   flat vectors.  Every product is formed in float64 from its fp32 operands (exact)
+ *   and added in plato_agg_trust_stats' fixed order, chunked by D alone.  Its
+ *   properties (a)-(d) hold: repeatable; the value for (r, j) depends only on row r,
+ *   vector j and D (and is the same bits with the two exchanged); within D * 2^-53 *
+ *   sum|terms| of the exact sum; NaN and +-inf propagate.  Each row is read once per
+ *   call, whatever m is.
+ *   d_rows, d_vecs   device arrays of R and of m flat-row pointers
+ *   d_workspace      plato_agg_rows_dots_workspace(R, m, D) bytes (0: bad arguments),
+ *                    256-byte aligned
+ *   d_out            R * m doubles, 16-byte aligned
+ *   1 <= R <= PLATO_AGG_DETECT_MAX_ROWS; 1 <= m <= PLATO_AGG_DETECT_MAX_VECTORS.
+ *
+ * plato_agg_lbfgs_predict  <- last_gradients + (sigma * v - [sigma * S.T, Y.T] @ c)
+ *   for every coordinate e: acc = +0; for j = 0..R-1 in table order:
+ *     acc = acc + d_a[j] * (double)rows[j][e]
+ *   pred[e] = (float)(((double)last_g[e] + sigma * (double)v[e]) - acc)
+ *   every multiplication and addition float64 and separately rounded.  d_a is a
+ *   device array of R doubles.
+ *
+ * plato_agg_delta_sqdist  <- torch.norm(pred_grad - flattened_deltas_attacked, dim=1)
+ *   d_out[k] = sum over e of ((double)pred[e] - (double)d_k[e])^2: the float64
+ *   difference and its square separately rounded, added in plato_agg_trust_stats'
+ *   fixed order (the fp32 region's chunks, then the int64 region's) with the same
+ *   four properties; client k's value depends only on row k, b, pred and
+ *   (n_f32, n_i64).
+ *   d_workspace      plato_agg_delta_sqdist_workspace(K, n_f32, n_i64) bytes
+ *   d_out            K doubles, 16-byte aligned
+ *
+ * All four: 1 <= K <= PLATO_AGG_ROBUST_MAX_K; fewer than 2^38 coordinates; no
+ * coordinates is a success that launches nothing and writes nothing.
+ *
+ * Documented divergences from the reference, all by rounding only: the means, the
+ * dots, the prediction and the distances are float64 sums rounded once where the
+ * reference's are fp32 (ATen's blocked sums, BLAS sgemm); the system is solved in
+ * float64 on the host where the reference inverts it in fp32.
+ */
+#define PLATO_AGG_DETECT_MAX_ROWS 65536
+#define PLATO_AGG_DETECT_MAX_VECTORS 4
+int plato_agg_detect_means(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                           const float* d_b_f32, const int64_t* d_b_i64,
+                           const float* d_last_w, const float* d_last_g, float* d_g, float* d_v,
+                           float* d_s_new, float* d_y_new, float* d_b_flat,
+                           size_t n_f32, size_t n_i64, hipStream_t stream);
+size_t plato_agg_rows_dots_workspace(int R, int m, size_t D);
+int plato_agg_rows_dots(const float* const* d_rows, int R, const float* const* d_vecs, int m, size_t D,
+                        void* d_workspace, double* d_out /* R * m */, hipStream_t stream);
+int plato_agg_lbfgs_predict(const float* const* d_rows, int R, const double* d_a /* R */, double sigma,
+                            const float* d_last_g, const float* d_v, float* d_pred, size_t D,
+                            hipStream_t stream);
+size_t plato_agg_delta_sqdist_workspace(int K, size_t n_f32, size_t n_i64);
+int plato_agg_delta_sqdist(const float* const* d_x_f32, const int64_t* const* d_x_i64, int K,
+                           const float* d_b_f32, const int64_t* d_b_i64, const float* d_pred,
+                           size_t n_f32, size_t n_i64, void* d_workspace, double* d_out /* K */,
+                           hipStream_t stream);
 
 /*
  * Sub-model aggregation (examples/model_search/{heterofl,fjord,fedrolex,anycostfl}:

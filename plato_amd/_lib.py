@@ -32,6 +32,8 @@ PLATO_AGG_ROBUST = {"median": 0, "nearest_mean": 1}
 PLATO_AGG_ROBUST_MAX_K = 256
 PLATO_AGG_PAIRDIST_CHAIN = 128
 PLATO_AGG_TRUST_TILE = 1024
+PLATO_AGG_DETECT_MAX_ROWS = 65536
+PLATO_AGG_DETECT_MAX_VECTORS = 4
 PLATO_AGG_SUBMODEL_MAX_K = 4096
 PLATO_AGG_SUBMODEL_TILE = 1024
 PLATO_AGG_SUBMODEL_ENTRY_WORDS = 6
@@ -192,6 +194,18 @@ SIGNATURES = {
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
     "plato_agg_add_scaled_rows": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_float, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
+    "plato_agg_detect_means": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                 _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
+    "plato_agg_rows_dots_workspace": (_c_size_t, [_c_int, _c_int, _c_size_t]),
+    "plato_agg_rows_dots": (
+        _c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
+    "plato_agg_lbfgs_predict": (
+        _c_int, [_c_void_p, _c_int, _c_void_p, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "plato_agg_delta_sqdist_workspace": (_c_size_t, [_c_int, _c_size_t, _c_size_t]),
+    "plato_agg_delta_sqdist": (
+        _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p,
+                 _c_void_p, _c_void_p]),
     "plato_agg_submodel_tables_bytes": (_c_size_t, [_c_int, _c_size_t]),
     "plato_agg_submodel_mean": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,

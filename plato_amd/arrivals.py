@@ -112,6 +112,24 @@ def adopt_rule(delta_key, holds_deltas: bool, has_baseline: bool, base_key, same
     return Adopt.REFUSE
 
 
+def stage_as_arrivals(engine, rnd, payloads) -> bool:
+    """Stage a round's clients in slot order as arrival rows, so that the round that follows on ``engine``
+    adopts them and nothing is staged twice (the detector server's attack simulation and filter, which run
+    ahead of the aggregation): the row staged at arrival if the round may use it, else a fresh arrival row;
+    a payload that does not fit the arrival slabs goes into the round's own slab.  Returns whether every
+    payload lies in an arrival row."""
+    in_arrival_rows = True
+    for slot, payload in enumerate(payloads):
+        if rnd.adopt(slot, payload):
+            continue
+        engine.drop_arrival(payload)  # staged as a delta, or written since: stage it again
+        if engine.prestage(payload, rnd.layout) and rnd.adopt(slot, payload):
+            continue
+        rnd.put_client(slot, payload)
+        in_arrival_rows = False
+    return in_arrival_rows
+
+
 def adopt_or_put(rnd, payloads, what: str | None = None) -> None:
     """Stage a round's clients in slot order: the copy staged at arrival if any, else the payload now."""
     extra = () if what is None else (what,)

@@ -1,4 +1,4 @@
-// rows.h — what robust.hip, krum.hip and trust.hip share: the kernels there all read K client rows through
+// rows.h — what robust.hip, krum.hip, trust.hip and detect.hip share: the kernels there all read K client rows through
 // a wave-uniform table of row pointers, an fp32 region and an int64 region promoted to fp32, and their
 // C-ABI entry points refuse the same malformed arguments with the same words.  Everything is in the
 // anonymous namespace, as it was in each of the three files: the kernels' symbols do not change.
@@ -67,6 +67,52 @@ inline uint32_t num_chunks(uint64_t n, uint64_t unit, uint32_t max_chunks) {
   const uint64_t len = chunk_len(n, unit, max_chunks);
   return n ? uint32_t((n + len - 1) / len) : 0;
 }
+
+// ------------------------------------------------------------------ the fixed-order float64 reduction
+// What trust.hip and detect.hip share, so that "the order of plato_agg_trust_stats" is one piece of code:
+// the shape of a workgroup (256 lanes, a batch of kU rows, kPer coordinates per lane and pass), the chunking
+// of a region by its coordinate count alone, the butterfly over a wave and the final kernel that adds the
+// chunks' partials in chunk order.
+namespace f64red {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kU = 8;                                 // rows per workgroup
+constexpr int kPer = 2;                               // coordinates per lane and pass
+constexpr uint64_t kTile = PLATO_AGG_TRUST_TILE;      // a chunk is a whole number of these
+constexpr uint64_t kPass = uint64_t(kThreads) * kPer;
+constexpr uint32_t kMaxChunks = 1024;                 // coordinate chunks per region, at most
+static_assert(kTile % kPass == 0, "a tile is a whole number of passes");
+
+// Coordinates per chunk of a region of n coordinates: a multiple of kTile, chosen by n alone.
+inline uint64_t region_chunk_len(uint64_t n) { return chunk_len(n, kTile, kMaxChunks); }
+inline uint32_t region_chunks(uint64_t n) { return num_chunks(n, kTile, kMaxChunks); }
+inline uint32_t num_batches(int rows) { return uint32_t(rows + kU - 1) / kU; }
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// out[row] = sum over the chunks, in chunk order, of the row's partials ws[chunk * nrows + row].  One
+// workgroup per row: the partials are fetched by all lanes at once and added by one, so the order costs LDS
+// reads, not a chain of memory round trips.  (A template so that only the files that launch it hold it.)
+template <int kBlock>
+__global__ __launch_bounds__(kBlock) void final_kernel(const double* __restrict__ ws, uint64_t nrows,
+                                                      uint32_t nchunks, double* __restrict__ out) {
+  __shared__ double part[2 * kMaxChunks];
+  const uint64_t row = blockIdx.x;
+  for (uint32_t c = threadIdx.x; c < nchunks; c += kBlock) part[c] = ws[uint64_t(c) * nrows + row];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sum = 0.0;
+    for (uint32_t c = 0; c < nchunks; ++c) sum += part[c];
+    out[row] = sum;
+  }
+}
+
+}  // namespace f64red
 
 // The refusals of the entry points.  Each returns its message, or nullptr for arguments it accepts; an
 // entry point lists its checks in the order it refuses in and reports the first (they only compare their

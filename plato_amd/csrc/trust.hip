@@ -23,25 +23,7 @@
 namespace {
 
 // ------------------------------------------------------------------ per-client dots and norms
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kU = 8;                                 // clients per workgroup
-constexpr int kPer = 2;                               // coordinates per lane and pass
-constexpr uint64_t kTile = PLATO_AGG_TRUST_TILE;      // a chunk is a whole number of these
-constexpr uint64_t kPass = uint64_t(kThreads) * kPer;
-constexpr uint32_t kMaxChunks = 1024;                 // coordinate chunks per region, at most
-static_assert(kTile % kPass == 0, "a tile is a whole number of passes");
-
-// Coordinates per chunk of a region of n coordinates: a multiple of kTile, chosen by n alone.
-uint64_t chunk_len(uint64_t n) { return chunk_len(n, kTile, kMaxChunks); }
-uint32_t num_chunks(uint64_t n) { return num_chunks(n, kTile, kMaxChunks); }
-uint32_t num_batches(int K) { return uint32_t(K + kU - 1) / kU; }
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
+using namespace f64red;  // rows.h: the workgroup shape, the chunking, wave_sum and the final kernel
 
 // One workgroup: client batch blockIdx.x (batch num_batches(K) is the reference vector's own) x chunk
 // blockIdx.y of one region.  ws[(chunk0 + chunk) * (3K + 1) + row] = the chunk's partial of output `row`.
@@ -137,22 +119,6 @@ __global__ __launch_bounds__(kThreads) void trust_stats_kernel(const typename Co
   }
 }
 
-// out[row] = sum over the chunks, in chunk order, of the row's partials.  One workgroup per row: the
-// partials are fetched by all lanes at once and added by one, so the order costs LDS reads, not a chain of
-// memory round trips.
-__global__ __launch_bounds__(256) void trust_final_kernel(const double* __restrict__ ws, uint32_t nrows,
-                                                         uint32_t nchunks, double* __restrict__ out) {
-  __shared__ double part[2 * kMaxChunks];
-  const uint32_t row = blockIdx.x;
-  for (uint32_t c = threadIdx.x; c < nchunks; c += 256) part[c] = ws[uint64_t(c) * nrows + row];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double sum = 0.0;
-    for (uint32_t c = 0; c < nchunks; ++c) sum += part[c];
-    out[row] = sum;
-  }
-}
-
 // ------------------------------------------------------------------ sum of scaled rows
 template <bool I64>
 __global__ __launch_bounds__(256) void scaled_sum_kernel(const typename Column<I64>::elem* const* x, int K,
@@ -177,7 +143,7 @@ extern "C" {
 
 size_t plato_agg_trust_stats_workspace(int K, size_t n_f32, size_t n_i64) {
   if (K < 1 || K > PLATO_AGG_ROBUST_MAX_K || n_f32 >= kMaxCoords || n_i64 >= kMaxCoords) return 0;
-  const size_t chunks = size_t(num_chunks(n_f32)) + num_chunks(n_i64);
+  const size_t chunks = size_t(region_chunks(n_f32)) + region_chunks(n_i64);
   const size_t bytes = chunks * (3 * size_t(K) + 1) * sizeof(double);
   return bytes ? bytes : 256;
 }
@@ -198,16 +164,16 @@ int plato_agg_trust_stats(const float* const* d_x_f32, const int64_t* const* d_x
   });
   if (why) return fail(PLATO_AGG_EINVAL, why);
   if (!n_f32 && !n_i64) return plato_agg_internal::clear_error();
-  const uint32_t cf = num_chunks(n_f32), ci = num_chunks(n_i64), nb = num_batches(K) + 1;
+  const uint32_t cf = region_chunks(n_f32), ci = region_chunks(n_i64), nb = num_batches(K) + 1;
   const uint32_t nrows = 3 * uint32_t(K) + 1;
   double* ws = static_cast<double*>(d_workspace);
   if (cf)
     hipLaunchKernelGGL((trust_stats_kernel<false>), dim3(nb, cf), dim3(kThreads), 0, stream, d_x_f32, K, d_ref_f32, eps,
-                       uint64_t(n_f32), chunk_len(n_f32), 0u, ws);
+                       uint64_t(n_f32), region_chunk_len(n_f32), 0u, ws);
   if (ci)
     hipLaunchKernelGGL((trust_stats_kernel<true>), dim3(nb, ci), dim3(kThreads), 0, stream, d_x_i64, K,
-                       d_ref_i64_as_f32, eps, uint64_t(n_i64), chunk_len(n_i64), cf, ws);
-  hipLaunchKernelGGL(trust_final_kernel, dim3(nrows), dim3(256), 0, stream, ws, nrows, cf + ci, d_out);
+                       d_ref_i64_as_f32, eps, uint64_t(n_i64), region_chunk_len(n_i64), cf, ws);
+  hipLaunchKernelGGL(final_kernel<256>, dim3(nrows), dim3(256), 0, stream, ws, nrows, cf + ci, d_out);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(PLATO_AGG_EHIP, std::string("trust_stats: ") + hipGetErrorString(err));
   return plato_agg_internal::clear_error();

@@ -190,6 +190,7 @@ class FedAvgEngine(RobustAggregates, SubmodelAggregates, ElasticAggregates):
         self._arrival_base: DeviceArena | None = None  # the model arrivals are turned into deltas against
         self._submodel = None                     # plato_amd.submodel's layouts, stagers and slab
         self._elastic = None                      # plato_amd.elastic's
+        self.fldetector = None                    # plato_amd.detectors.FLDetectorState, kept across rounds
 
     # ----------------------------------------------------------- allocation
     def _prepare(self, template: Mapping[str, torch.Tensor], k: int, codec: str = "native") -> ArenaLayout:

@@ -437,6 +437,9 @@ class MultiRound:
     def launch_fltrust(self, order=None):
         raise NotImplementedError("robust aggregation (Fl-trust) runs on one GPU: use FedAvgEngine")
 
+    def launch_fldetector(self, received_ids, order=None):
+        raise NotImplementedError("the FLDetector defence runs on one GPU: use FedAvgEngine")
+
     def __init__(self, engine: MultiDeviceEngine, layout: ArenaLayout, capacity: int, codec: str):
         self.engine = engine
         self.layout = layout

@@ -5,6 +5,8 @@ host (``plato_amd.krum``, ``plato_amd.trust``), an all-float32 result.  :class:`
 as a mixin of ``engine.AggregationRound``, :class:`RobustAggregates` the one-call forms of ``FedAvgEngine``.
 ``launch_attack`` is the attack simulation that the example runs before them (examples/detector/attacks.py):
 it poisons the attackers' staged rows in place, and the aggregators then read those rows.
+``launch_fldetector`` is the defence that runs between the two (examples/detector/detectors.py: fl_detector):
+it scores the staged rows against the engine's record (``plato_amd.detectors``) and changes none.
 """
 
 from __future__ import annotations
@@ -302,6 +304,37 @@ class RobustLaunches:
                       *self._sizes(stream))
         info.update(s=np.float32(s), vector=(v_f[:n_f], v_i[:n_i]), poisoned=True)
         self._attack_keep = (df, di, dtf, dti, tf, ti)  # until the stream has passed the launches
+
+    def launch_fldetector(self, received_ids: Sequence, order: Sequence[int] | None = None) -> None:
+        """``detectors.fl_detector`` of the reference's detector example (examples/detector/detectors.py:
+        310-418) over the staged client rows, ``received_ids`` their client ids in the same order.  The
+        round holds weights and its baseline.  One pass forms the mean update, the mean step and the
+        record's next rows (``plato_agg_detect_means``), one the dots that extend the record's Gram cache
+        and give the right-hand side (``plato_agg_rows_dots``); the 2N x 2N system is solved on the host
+        (``plato_amd.detectors``), ``plato_agg_lbfgs_predict`` forms the predicted update and
+        ``plato_agg_delta_sqdist`` every client's squared distance to it; the scores and their 2-means
+        split are the host's.  The record (``engine.fldetector``, a
+        :class:`plato_amd.detectors.FLDetectorState`) is kept across rounds; the first round only starts
+        it and flags nobody.  ``self.detector`` holds ``distances``, ``scores``, ``malicious`` (positions
+        in ``order``), ``sigma``, ``cond`` and the device regions of the prediction (``pred``).
+        Synchronises; nothing is aggregated and no row is changed."""
+        from .detectors import FLDetectorState
+
+        if not self.has_baseline:
+            raise ValueError("launch_fldetector forms the clients' deltas: stage the baseline first")
+        slots, tf, ti, stream = self._robust_rows("launch_fldetector", order)
+        received_ids = list(received_ids)
+        if len(received_ids) != len(slots):
+            raise ValueError(f"launch_fldetector: {len(received_ids)} client ids for {len(slots)} rows")
+        engine = self.engine
+        if engine.fldetector is None:
+            engine.fldetector = FLDetectorState()
+        state = engine.fldetector
+        try:
+            self.detector = engine.last_detector = state.round(self, tf, ti, len(slots), received_ids, stream)
+        finally:
+            stream.synchronize()
+            self._resolve_timers()
 
     def fetch_rows(self, slots: Sequence[int]):
         """[(fp32 region, int64 region)] of the staged rows ``slots`` as host tensors, stream-ordered

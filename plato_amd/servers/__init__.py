@@ -2,7 +2,7 @@
 
 from .fedavg import DeltasAggregationMixin, FusedAggregationMixin, make_server  # noqa: F401
 from .ingest import WireIngestMixin  # noqa: F401
-from .robust import (AttackSimulationMixin, DetectorAggregationMixin, RobustAggregationMixin,  # noqa: F401
-                     TrustAggregationMixin)
+from .robust import (AttackSimulationMixin, DetectorAggregationMixin, DetectorFilterMixin,  # noqa: F401
+                     RobustAggregationMixin, TrustAggregationMixin)
 from .elastic import ElasticAggregationMixin  # noqa: F401
 from .submodel import SubmodelAggregationMixin  # noqa: F401

@@ -13,13 +13,14 @@ every client by its clipped cosine with the mean model (``plato_agg_mean_rows``,
 ``plato_agg_trust_stats``, the scalars on the host in ``plato_amd.trust``, ``plato_agg_scaled_sum``); it is
 :class:`TrustAggregationMixin`'s, which again adds it to its parent's.  One ``aggregate_weights`` serves
 the three: a class differs in its table of names only.  The detector server's ``weights_received``
-pipeline runs before this hook; its filters are the base class's, unchanged, and its attack simulation
-(``weights_attacked``) runs on the GPU with :class:`AttackSimulationMixin` for the attacks "LIE",
-"Lambda_attack", "Min-Max" and "Min-Sum" (``plato_amd.attacks``)::
+pipeline runs before this hook: its attack simulation (``weights_attacked``) runs on the GPU with
+:class:`AttackSimulationMixin` for the attacks "LIE", "Lambda_attack", "Min-Max" and "Min-Sum"
+(``plato_amd.attacks``), its filter (``weights_filter``) with :class:`DetectorFilterMixin` for the defence
+"FLDetector" (``plato_amd.detectors``); every other attack and defence is the base class's, unchanged::
 
     Server = make_server(base=detector_server.Server, mixin=RobustAggregationMixin)
 
-    class Mixin(AttackSimulationMixin, DetectorAggregationMixin):
+    class Mixin(DetectorFilterMixin, AttackSimulationMixin, DetectorAggregationMixin):
         pass
     Server = make_server(base=detector_server.Server, mixin=Mixin)
 """
@@ -28,7 +29,7 @@ from __future__ import annotations
 
 from .. import tracing
 from ..arena import payload_codec
-from ..arrivals import adopt_or_put
+from ..arrivals import adopt_or_put, stage_as_arrivals
 from .fedavg import FusedAggregationMixin, _EngineHolder
 
 
@@ -205,16 +206,8 @@ class AttackSimulationMixin(_EngineHolder):
         rnd = engine.begin(baseline, len(payloads))
         rnd.deltas = False  # the rows stay weights: the deltas are formed in scratch
         rnd.put_baseline(baseline)
-        in_arrival_rows = True
         with tracing.range("plato_amd.attack.stage"):
-            for slot, payload in enumerate(payloads):
-                if rnd.adopt(slot, payload):
-                    continue
-                engine.drop_arrival(payload)  # staged as a delta, or written since: stage it again
-                if engine.prestage(payload, rnd.layout) and rnd.adopt(slot, payload):
-                    continue
-                rnd.put_client(slot, payload)
-                in_arrival_rows = False
+            in_arrival_rows = stage_as_arrivals(engine, rnd, payloads)
         with tracing.range("plato_amd.attack.launch"):
             rnd.launch_attack(kind, range(len(payloads)), **params)
         if self.attack_writeback or multi or not in_arrival_rows:
@@ -226,3 +219,57 @@ class AttackSimulationMixin(_EngineHolder):
                     engine.refresh_arrival(payload)
         self._plato_amd_attack = dict(rnd.attack, timings=dict(rnd.timings))
         return weights_received
+
+
+def _detector_type():
+    """``Config().server.detector_type``, or None where it is not set or Plato is not installed."""
+    try:
+        from plato.config import Config
+    except ImportError:
+        return None
+    return getattr(Config().server, "detector_type", None)
+
+
+class DetectorFilterMixin(_EngineHolder):
+    """``weights_filter`` of the detector server (detector_server.py:137-175) on the GPU for the defence
+    "FLDetector" of ``server.detector_type`` (``detectors.fl_detector``); every other name and no defence
+    at all go to the base class unchanged.
+
+    The received payloads are staged as arrival rows (or adopted, where the attack simulation or the
+    arrival hook staged them), scored there (``AggregationRound.launch_fldetector``) and the payloads that
+    were not flagged are returned in order.  The aggregation hook that follows adopts their rows: nothing
+    is staged twice.  The record is the engine's (``engine.fldetector``) and is kept across rounds.
+    Composes with :class:`AttackSimulationMixin` and the aggregation mixins by inheritance.
+    """
+
+    #: None = ``Config().server.detector_type``
+    detector_type = None
+
+    def weights_filter(self, weights_attacked):
+        from .. import _lib
+
+        own = self.detector_type
+        name = own if own is not None else _detector_type()
+        if name != "FLDetector":
+            return super().weights_filter(weights_attacked)
+        codec = payload_codec(weights_attacked[0])
+        if codec != "native":
+            raise ValueError(f"the FLDetector defence takes native payloads, not {codec} codes")
+        engine = self.aggregation_engine()
+        if getattr(engine, "primary", None) is not None:
+            raise NotImplementedError("the FLDetector defence runs on one GPU (aggregation_devices has several)")
+        if len(weights_attacked) > _lib.PLATO_AGG_ROBUST_MAX_K:
+            raise ValueError(f"the FLDetector defence takes at most {_lib.PLATO_AGG_ROBUST_MAX_K} clients, "
+                             f"got {len(weights_attacked)}")
+        baseline = self.algorithm.extract_weights()
+        received_ids = [update.client_id for update in self.updates]
+        rnd = engine.begin(baseline, len(weights_attacked))
+        rnd.deltas = False  # the rows stay weights: the deltas are formed in registers
+        rnd.put_baseline(baseline)
+        with tracing.range("plato_amd.detector.stage"):
+            stage_as_arrivals(engine, rnd, weights_attacked)
+        with tracing.range("plato_amd.detector.launch"):
+            rnd.launch_fldetector(received_ids)
+        flagged = set(rnd.detector["malicious"])
+        self._plato_amd_detector = dict(rnd.detector, timings=dict(rnd.timings))
+        return [payload for i, payload in enumerate(weights_attacked) if i not in flagged]
