@@ -898,6 +898,61 @@ int plato_agg_delta_sqdist(const float* const* d_x_f32, const int64_t* const* d_
                            hipStream_t stream);
 
 /*
+ * Global magnitude pruning (plato/processors/unstructured_pruning.py, the
+ * "unstructured_pruning" outbound processor: torch.nn.utils.prune.global_unstructured
+ * with L1Unstructured): of all prunable weights together, the k with the smallest
+ * magnitude become zero.
+ *
+ * plato_agg_prune_global  <- torch.topk(|w|, k, largest=False) over the concatenated
+ *                            weights, then w * mask
+ *   works in place on one fp32 row of n_row elements.  The prunable elements are the
+ *   pieces [begin, end) of h_pieces (elements of the row; `entry` is not read), taken
+ *   in table order: that order is the flat index, and n their total count.  Pieces
+ *   are ascending and disjoint; they may be empty and need not start on a 16-byte
+ *   boundary.  Every element of the row outside the pieces keeps its bits.
+ *
+ *   key(w) = bits(w) & 0x7fffffff, compared as an unsigned integer: |w| in torch.topk's
+ *   order, NaN largest.  T is the key of rank k - 1 (0-based) in the ascending order of
+ *   the n keys.  An element is pruned if key < T; of the elements with key == T, the
+ *   r = k - #(key < T) with the lowest flat indices are pruned (torch.topk's choice
+ *   among them is unspecified).  Exactly k elements are pruned.  Only integer
+ *   comparisons and integer sums decide: the result is the same bits on every run.
+ *
+ *   A pruned element becomes w * 0.0f as x86-64 evaluates it, formed from the bits:
+ *   bits & 0x80000000 for a finite w (a negative weight gives -0.0), bits | 0x00400000
+ *   for a NaN (quieted; sign and payload kept), 0xffc00000 for +-inf.  Every other
+ *   element keeps its bits (the reference's w * 1.0f quiets a signalling NaN; this
+ *   does not).
+ *
+ *   T is found by a radix select over the pieces in HBM, most significant digit first,
+ *   in 3 passes (11, 10 and 10 bits); with the masked write and, only when
+ *   0 < r < #(key == T), one more read that ranks the ties, the row is read 4 or 5
+ *   times and written once.  All launches are ordered by `stream`; nothing returns to
+ *   the host between them.
+ *
+ *   h_pieces     HOST table of n_pieces rows; it is uploaded on `stream` ahead of the
+ *                kernels, so it stays unchanged until the stream reaches them
+ *   d_workspace  plato_agg_prune_global_workspace(n_pieces, n) bytes (0: bad
+ *                arguments), 256-byte aligned
+ *   d_result     4 uint64, 16-byte aligned: T, #(key < T), #(key == T), r
+ *   The table is checked before any GPU work (PLATO_AGG_EINVAL, message in
+ *   plato_agg_last_error): a piece with end < begin, pieces that overlap or are out
+ *   of order, a piece past n_row, k > n, more than 2^20 pieces, n_row >=
+ *   2^32 (the counters and the piece table are 32-bit; n <= n_row).  k = 0 is a
+ *   success that launches nothing and writes nothing, d_result included; k = n prunes
+ *   every element.  d_row is 16-byte aligned.
+ *
+ *   A streaming launch has at most PLATO_AGG_PRUNE_GRID workgroups, each taking
+ *   PLATO_AGG_PRUNE_TILE elements per grid step.
+ */
+#define PLATO_AGG_PRUNE_TILE 4096
+#define PLATO_AGG_PRUNE_GRID 1024
+#define PLATO_AGG_PRUNE_MAX_ELEMENTS 0xffffffffull
+size_t plato_agg_prune_global_workspace(size_t n_pieces, size_t n_total);
+int plato_agg_prune_global(float* d_row, size_t n_row, const plato_agg_chunk* h_pieces, size_t n_pieces, size_t k,
+                           void* d_workspace, uint64_t* d_result /* 4 */, hipStream_t stream);
+
+/*
  * Sub-model aggregation (examples/model_search/{heterofl,fjord,fedrolex,anycostfl}:
  * Algorithm.aggregation): every client sends leading-corner boxes
  * value[:s0, :s1, ...] of the global tensors, and every global element becomes the

@@ -34,6 +34,9 @@ PLATO_AGG_PAIRDIST_CHAIN = 128
 PLATO_AGG_TRUST_TILE = 1024
 PLATO_AGG_DETECT_MAX_ROWS = 65536
 PLATO_AGG_DETECT_MAX_VECTORS = 4
+PLATO_AGG_PRUNE_TILE = 4096
+PLATO_AGG_PRUNE_GRID = 1024
+PLATO_AGG_PRUNE_MAX_ELEMENTS = 0xFFFFFFFF
 PLATO_AGG_SUBMODEL_MAX_K = 4096
 PLATO_AGG_SUBMODEL_TILE = 1024
 PLATO_AGG_SUBMODEL_ENTRY_WORDS = 6
@@ -206,6 +209,9 @@ SIGNATURES = {
     "plato_agg_delta_sqdist": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_size_t, _c_void_p,
                  _c_void_p, _c_void_p]),
+    "plato_agg_prune_global_workspace": (_c_size_t, [_c_size_t, _c_size_t]),
+    "plato_agg_prune_global": (
+        _c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
     "plato_agg_submodel_tables_bytes": (_c_size_t, [_c_int, _c_size_t]),
     "plato_agg_submodel_mean": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,
