@@ -953,6 +953,65 @@ int plato_agg_prune_global(float* d_row, size_t n_row, const plato_agg_chunk* h_
                            void* d_workspace, uint64_t* d_result /* 4 */, hipStream_t stream);
 
 /*
+ * QSGD quantizer (plato/processors/model_quantize_qsgd.py, the "model_quantize_qsgd"
+ * outbound processor: Processor._process_layer): every entry of a state_dict becomes
+ * its maximum magnitude and one byte per element, stochastically rounded to one of
+ * `level` magnitudes.  plato_agg_fedavg_qsgd and plato_agg_decode_rows read these codes.
+ *
+ * plato_agg_qsgd_encode  <- max_v = max|layer|, level = ceil(|v| / max_v * (s - 1) - 1),
+ *                           zeta = level + (random() <= |v| / max_v * (s - 1) - level),
+ *                           the sign, one byte per value
+ *   reads one fp32 row of n_row elements.  The entries are the pieces [begin, end) of
+ *   h_pieces (elements of the row; `entry` is not read).  Pieces are ascending and
+ *   disjoint; they may be empty and need not start on a 16-byte boundary.  d_codes[i] is
+ *   the code of d_row[i]: every byte of d_codes outside the pieces keeps its value.
+ *
+ *   d_max_key[p] = max over piece p of bits(v) & 0x7fffffff, as an unsigned integer: the
+ *   bits of m = max |v| when every value is finite.  0 marks an all-zero (or empty)
+ *   piece, a key >= 0x7f800000 a piece that holds an infinity or a NaN.
+ *
+ *   With tp = (float)(level - 1), every operation a separately rounded fp32 operation
+ *   (nothing is contracted to an fma):
+ *     x    = (|v| / m) * tp                  IEEE division, subnormals kept
+ *     lvl  = ceil(x - 1)                     -1 when x - 1 rounds to -1: then p = 1
+ *     p    = x - lvl                         in (0, 1]
+ *     mag  = lvl + (u <= p ? 1 : 0)          in [0, level - 1]
+ *     code = mag | (0x80 if v < 0 and mag > 0)     -0.0 and a negative that rounds to 0
+ *                                                  give 0x00, never 0x80
+ *   u of row element i depends on (seed, i) alone, not on the pieces:
+ *     h = splitmix64(key + (i >> 1)), key as plato_agg_fill_synth_* derives it from
+ *         (seed, stream 0x51534744)
+ *     u = (float)((i even ? h >> 40 : h >> 16) & 0xffffff) * 2^-24
+ *   An all-zero piece gets zero codes (the reference fails on one).  A non-finite piece
+ *   gets unspecified codes, inside the piece only.  Only integer maxima are reduced: the
+ *   codes and the maxima are the same bytes on every run and for every grid.
+ *
+ *   The row is read twice and one byte per element is written.  All launches are
+ *   ordered by `stream`; nothing returns to the host between them.
+ *
+ *   h_pieces     HOST table of n_pieces rows; it is uploaded on `stream` ahead of the
+ *                kernels, so it stays unchanged until the stream reaches them
+ *   d_codes      n_row bytes, 4-byte aligned
+ *   d_max_key    n_pieces uint32
+ *   d_workspace  plato_agg_qsgd_encode_workspace(n_pieces, n) bytes (0: bad arguments),
+ *                256-byte aligned; n is the pieces' total count
+ *   The arguments are checked before any GPU work (PLATO_AGG_EINVAL, message in
+ *   plato_agg_last_error): a level outside [2, 128], a piece with end < begin, pieces
+ *   that overlap or are out of order, a piece past n_row, more than 2^20 pieces, n_row
+ *   >= 2^32, a null or misaligned pointer (d_row: 16 bytes).  n_pieces = 0 or n = 0 is
+ *   a success that launches nothing and writes nothing, d_max_key included.
+ *
+ *   A streaming launch has at most PLATO_AGG_QSGD_ENCODE_GRID workgroups, each taking
+ *   PLATO_AGG_QSGD_ENCODE_TILE elements per grid step.
+ */
+#define PLATO_AGG_QSGD_ENCODE_TILE 4096
+#define PLATO_AGG_QSGD_ENCODE_GRID 1024
+size_t plato_agg_qsgd_encode_workspace(size_t n_pieces, size_t n_total);
+int plato_agg_qsgd_encode(const float* d_row, size_t n_row, const plato_agg_chunk* h_pieces, size_t n_pieces,
+                          int level, uint64_t seed, uint8_t* d_codes /* n_row */, uint32_t* d_max_key /* n_pieces */,
+                          void* d_workspace, hipStream_t stream);
+
+/*
  * Sub-model aggregation (examples/model_search/{heterofl,fjord,fedrolex,anycostfl}:
  * Algorithm.aggregation): every client sends leading-corner boxes
  * value[:s0, :s1, ...] of the global tensors, and every global element becomes the

@@ -37,6 +37,8 @@ PLATO_AGG_DETECT_MAX_VECTORS = 4
 PLATO_AGG_PRUNE_TILE = 4096
 PLATO_AGG_PRUNE_GRID = 1024
 PLATO_AGG_PRUNE_MAX_ELEMENTS = 0xFFFFFFFF
+PLATO_AGG_QSGD_ENCODE_TILE = 4096
+PLATO_AGG_QSGD_ENCODE_GRID = 1024
 PLATO_AGG_SUBMODEL_MAX_K = 4096
 PLATO_AGG_SUBMODEL_TILE = 1024
 PLATO_AGG_SUBMODEL_ENTRY_WORDS = 6
@@ -212,6 +214,10 @@ SIGNATURES = {
     "plato_agg_prune_global_workspace": (_c_size_t, [_c_size_t, _c_size_t]),
     "plato_agg_prune_global": (
         _c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_size_t, _c_void_p, _c_void_p, _c_void_p]),
+    "plato_agg_qsgd_encode_workspace": (_c_size_t, [_c_size_t, _c_size_t]),
+    "plato_agg_qsgd_encode": (
+        _c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_u64, _c_void_p, _c_void_p, _c_void_p,
+                 _c_void_p]),
     "plato_agg_submodel_tables_bytes": (_c_size_t, [_c_int, _c_size_t]),
     "plato_agg_submodel_mean": (
         _c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p,
